@@ -21,11 +21,14 @@ N > 1: the headline keeps the global batch at B = 2048 pairs per step and divide
 (tables / graph sharded: "scaling": "strong", north_star's partition); the data-parallel run (N x B pairs per step,
 weak) is the `dp` sub-record.
 
-One JSON line on rank 0: the contract fields, `roofline` (dominant kernel: CSR SpMM, HBM-bound, algorithmic bytes per
-launch / mean launch duration from HIP events on the launch stream), `cpu_baseline` (the reference's own train() step
-when a checkout is staged on this box, else the oracle port, on this host's cores), `eval`.  The parts live in
-benchlib/: workload (flags, data, step driver), launch (N ranks, watchdog), probes (roofline), evalbench, baseline,
-dropin_bench."""
+One JSON line on rank 0.  A plain run sets up, warms up, times the --steps steps and prints the contract fields (`metric`,
+`value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step`: milliseconds per timed step), the configuration and the last
+step's losses; `--dump-outputs DIR` also writes the tables and losses that last step left (DIR/<name>.npy).  `--full`
+adds the companion measurements: `roofline` (dominant kernel: CSR SpMM, HBM-bound, algorithmic bytes per launch / mean
+launch duration from HIP events on the launch stream), `steady_state`, `value_split16`, the N > 1 sub-records,
+`cpu_baseline` (the reference's own train() step when a checkout is staged on this box, else the oracle port, on this
+host's cores), `eval` and the drop-in tiers.  The parts live in benchlib/: workload (flags, data, step driver, output
+dump), launch (N ranks, watchdog), probes (roofline), evalbench, baseline, dropin_bench."""
 import json
 import os
 import sys
@@ -42,7 +45,8 @@ from benchlib.evalbench import eval_cpu_baseline, eval_throughput, eval_throughp
 from benchlib.launch import (Watchdog, default_layout_is_dp, first_steps_guarded, free_port,  # noqa: E402,F401
                              refuse_gpu_count, relaunch_under_torchrun)
 from benchlib.probes import (git_blob_hash, pmc_traffic_cols, spmm_roofline, time_spmm_kernel)  # noqa: E402,F401
-from benchlib.workload import (Runner, build_data, parse, spmm_alg_bytes, steady_state, step_alg_bytes)  # noqa: E402,F401
+from benchlib.workload import (Runner, build_data, dump_outputs, parse, spmm_alg_bytes, steady_state,  # noqa: E402,F401
+                               step_alg_bytes)
 
 NCE_MODELS = ("XSimGCL", "SimGCL", "SGL")
 
@@ -69,7 +73,7 @@ def launch_check(args, rank, world, backend, wd_seconds, coll_timeout):
                                        "global_batch": args.batch * (world if head == "dp" else 1),
                                        "parallelism": describe_layout(args.emb, world, head)},
                           "baseline_partition": baseline_partition_note(pick_layout(args.emb, world, head, None)),
-                          "sub_records": sub_record_layouts(args, world, head)}), flush=True)
+                          "sub_records": sub_record_layouts(args, world, head) if args.full else []}), flush=True)
     dist.barrier()
     dist.destroy_process_group()
     wd.stop()
@@ -232,12 +236,13 @@ def main():
         runner.fence()
     g = trainer.graph
     dp = bool(getattr(trainer, "dp", False))
-    # The roofline probes (per-flavour launch times, the gather bound, the stream rates: ~30 ms of launches the line needs
-    # anyway) run HERE, between the first warm-up steps and the rest: the timed region then starts on a chip that has been
-    # busy, not on one that idled through graph capture (profiles/r04_b_step_timeline.txt: after >= 0.3 s of idle the first
-    # 60 steps run 4 / 2.5 / 1.5 % slow -- DVFS ramp).
+    # The roofline probes (--full: per-flavour launch times, the gather bound, the stream rates: ~30 ms of launches) run HERE,
+    # between the first warm-up steps and the rest: the timed region then starts on a chip that has been busy, not on one
+    # that idled through graph capture (profiles/r04_b_step_timeline.txt: after >= 0.3 s of idle the first 60 steps run
+    # 4 / 2.5 / 1.5 % slow -- DVFS ramp).  A plain run goes straight on to its warm-up steps (and, for a region shorter than
+    # an epoch, the steps that align it with an epoch boundary).
     roof = None
-    if rank == 0:
+    if rank == 0 and args.full:
         try:
             roof = spmm_roofline(args, trainer, sharded, dp, None, g)
         except RuntimeError as e:             # (never lose a multi-GPU line to its footnotes)
@@ -249,6 +254,11 @@ def main():
     rec, elapsed = timed_record(trainer, runner, "headline")
     losses = trainer.read_losses()
     step_s = max(elapsed / args.steps, 1e-6)
+    dumped = None
+    if args.dump_outputs:                          # (before any later step moves the tables)
+        dumped = dump_outputs(args.dump_outputs, trainer, losses, write=rank == 0)
+        if watchdog is not None:
+            watchdog.beat("outputs dumped")
 
     out = {
         "metric": f"train pairs/sec ({args.model}, {'Yelp2018' if args.shape == 'yelp2018' else args.shape}-shape)",
@@ -277,88 +287,96 @@ def main():
                                   else [int(v) for v in trainer.xcd_shares])},
         "ms_per_step_by_rank": rec["ms_per_step_by_rank"],
         "final_losses": {"bpr": losses[0], "reg": losses[1], "cl": losses[2]},
+        **({"dumped_outputs": {"dir": args.dump_outputs, "shapes": dumped}} if dumped else {}),
     }
     if watchdog is not None:
         watchdog.partial = out                     # (from here on a hang in a later leg still leaves this line)
-    out["steady_state"] = steady_state(runner, step_s, rec["global_batch"])
-    out["value_steady_state"] = out["steady_state"]["pairs_per_s"]
-    if has_nce and not sharded:
-        # the same step with InfoNCE's two products on 16-bit split operands (the library's faster mode; re-captured graph)
-        trainer.set_nce_precision("split")
-        runner.run(20); runner.fence()
-        n16 = max(300, args.steps)
-        dt16, _, _ = runner.timed(n16, "split16 region")
-        out["value_split16"] = round(n16 * args.batch / dt16, 1)
-        out["ms_per_step_split16"] = round(dt16 / n16 * 1e3, 4)
-        out["config"]["value_split16"] = out["value_split16"]
-        trainer.set_nce_precision("f32")
-        runner.run(5); runner.fence()
-    if rank == 0 and roof:
-        if "step_alg_bytes" in roof:
-            roof["step_GBps"] = round(roof["step_alg_bytes"] / step_s / 1e9, 1)
-        out["roofline"] = roof
+    # ---- --full: everything beside the headline (a plain run has what its headline needs by now)
+    if args.full:
+        out["steady_state"] = steady_state(runner, step_s, rec["global_batch"])
+        out["value_steady_state"] = out["steady_state"]["pairs_per_s"]
+        if has_nce and not sharded:
+            # the same step with InfoNCE's two products on 16-bit split operands (the library's faster mode; re-captured graph)
+            trainer.set_nce_precision("split")
+            runner.run(20); runner.fence()
+            n16 = max(300, args.steps)
+            dt16, _, _ = runner.timed(n16, "split16 region")
+            out["value_split16"] = round(n16 * args.batch / dt16, 1)
+            out["ms_per_step_split16"] = round(dt16 / n16 * 1e3, 4)
+            out["config"]["value_split16"] = out["value_split16"]
+            trainer.set_nce_precision("f32")
+            runner.run(5); runner.fence()
+        if rank == 0 and roof:
+            if "step_alg_bytes" in roof:
+                roof["step_GBps"] = round(roof["step_alg_bytes"] / step_s / 1e9, 1)
+            out["roofline"] = roof
 
-    # ---- N > 1: the other layouts, each a record of its own next to the headline
-    for sub in sub_record_layouts(args, world, head) if sharded else []:
-        dist.barrier()
-        try:
-            from selfrec_amd.dist import pick_layout
-            chosen = pick_layout(args.emb, world, sub, nnz_adj)
-            s_tr, s_run, s_note = first_steps_guarded(make(chosen), lambda t: Runner(t, args.seed, dist, watchdog), watchdog,
-                                                      f"sub-record {chosen}")
-            s_rec, s_dt = timed_record(s_tr, s_run, f"sub-record {chosen}")
-            s_rec.update(layout=chosen, n_gpus=world, parallelism=parallelism_of(s_tr))
-            s_rec["steady_state"] = steady_state(s_run, max(s_dt / args.steps, 1e-6), s_rec["global_batch"])
-            if s_note:
-                s_rec["note"] = s_note
-            out["dp" if chosen == "dp" else f"layout_{chosen.replace(':', '_')}"] = s_rec
-            del s_tr, s_run
-        except Exception as e:                    # (never lose the headline to a companion record)
-            out[f"layout_{sub}_error"] = f"{type(e).__name__}: {e}"
-        if watchdog is not None:
-            watchdog.beat(f"sub-record {sub}")
-        dist.barrier()
-
-    if rank == 0:
-        small = len(raw[0]) <= 5_000_000
-        if not args.no_eval and not sharded and small:
-            out["eval"] = eval_throughput(trainer, data)
-            if out["eval"]:
-                # eval time runs "up to and including the python rec_list" -- the materialised figure is the
-                # metric; the lazy one is what fast_evaluation() pays per epoch
-                out["eval_users_per_s"] = out["eval"]["end_to_end_materialised_users_per_s"]
-                out["eval_users_per_s_lazy"] = out["eval"]["end_to_end_users_per_s"]
-                out["config"]["eval_users_per_s"] = out["eval_users_per_s"]
-        if not sharded and not args.no_dropin and args.model == "XSimGCL" and small:
-            out["dropin"] = dropin_throughput(args, raw)
-            out["dropin_pairs_per_s"] = out["dropin"]["pairs_per_s"]
-            out["dropin_fused"] = dropin_fused_throughput(args, raw)
-            out["dropin_fused_pairs_per_s"] = out["dropin_fused"]["pairs_per_s"]
-        # the CPU baseline rides on rank 0 at every N (the other ranks wait at the barrier below: ~15 s)
-        if not args.no_cpu_baseline and not small:
-            out["cpu_baseline"] = {"value": None, "unit": "pairs/s", "kind": "port", "cores": torch.get_num_threads(),
-                                   "sample": "not run at this shape: the reference's step needs ~25 GB of python objects and "
-                                             "minutes per step (tests/golden/make_golden_shapes.py ran it once: 216 s on 8 threads)"}
-        elif not args.no_cpu_baseline:
-            if watchdog is not None:
-                watchdog.beat("cpu baseline (rank 0 alone)")
-            out["cpu_baseline"] = cpu_baseline(args, raw, min(args.cpu_seconds, max(5.0, wd_seconds / 4)) if sharded
-                                               else args.cpu_seconds)
-            if out.get("eval"):
-                out["eval"]["cpu_baseline"] = eval_cpu_baseline(trainer, data)
-    if watchdog is not None:
-        watchdog.beat("cpu baseline")
-    if dist is not None:
-        dist.barrier()
-        if watchdog is not None:
-            watchdog.beat("after baseline barrier")
-        if not args.no_eval:
+        # ---- N > 1: the other layouts, each a record of its own next to the headline
+        for sub in sub_record_layouts(args, world, head) if sharded else []:
+            dist.barrier()
             try:
-                ev = eval_throughput_sharded(trainer, data, dist, rank, world)      # every rank takes part
-            except Exception as e:                # (never lose the training line to the evaluation leg)
-                ev = {"error": f"{type(e).__name__}: {e}"}
-            if rank == 0:
-                out["eval"] = ev
+                from selfrec_amd.dist import pick_layout
+                chosen = pick_layout(args.emb, world, sub, nnz_adj)
+                s_tr, s_run, s_note = first_steps_guarded(make(chosen), lambda t: Runner(t, args.seed, dist, watchdog), watchdog,
+                                                          f"sub-record {chosen}")
+                s_rec, s_dt = timed_record(s_tr, s_run, f"sub-record {chosen}")
+                s_rec.update(layout=chosen, n_gpus=world, parallelism=parallelism_of(s_tr))
+                s_rec["steady_state"] = steady_state(s_run, max(s_dt / args.steps, 1e-6), s_rec["global_batch"])
+                if s_note:
+                    s_rec["note"] = s_note
+                out["dp" if chosen == "dp" else f"layout_{chosen.replace(':', '_')}"] = s_rec
+                del s_tr, s_run
+            except Exception as e:                    # (never lose the headline to a companion record)
+                out[f"layout_{sub}_error"] = f"{type(e).__name__}: {e}"
+            if watchdog is not None:
+                watchdog.beat(f"sub-record {sub}")
+            dist.barrier()
+
+        if rank == 0:
+            small = len(raw[0]) <= 5_000_000
+            if not args.no_eval and not sharded and small:
+                out["eval"] = eval_throughput(trainer, data)
+                if out["eval"]:
+                    # eval time runs "up to and including the python rec_list" -- the materialised figure is the
+                    # metric; the lazy one is what fast_evaluation() pays per epoch
+                    out["eval_users_per_s"] = out["eval"]["end_to_end_materialised_users_per_s"]
+                    out["eval_users_per_s_lazy"] = out["eval"]["end_to_end_users_per_s"]
+                    out["config"]["eval_users_per_s"] = out["eval_users_per_s"]
+            if not sharded and not args.no_dropin and args.model == "XSimGCL" and small:
+                out["dropin"] = dropin_throughput(args, raw)
+                out["dropin_pairs_per_s"] = out["dropin"]["pairs_per_s"]
+                out["dropin_fused"] = dropin_fused_throughput(args, raw)
+                out["dropin_fused_pairs_per_s"] = out["dropin_fused"]["pairs_per_s"]
+            # the CPU baseline rides on rank 0 at every N (the other ranks wait at the barrier below: ~15 s)
+            if not args.no_cpu_baseline and not small:
+                out["cpu_baseline"] = {"value": None, "unit": "pairs/s", "kind": "port", "cores": torch.get_num_threads(),
+                                       "sample": "not run at this shape: the reference's step needs ~25 GB of python objects "
+                                                 "and minutes per step (tests/golden/make_golden_shapes.py ran it once: 216 s "
+                                                 "on 8 threads)"}
+            elif not args.no_cpu_baseline:
+                if watchdog is not None:
+                    watchdog.beat("cpu baseline (rank 0 alone)")
+                out["cpu_baseline"] = cpu_baseline(args, raw, min(args.cpu_seconds, max(5.0, wd_seconds / 4)) if sharded
+                                                   else args.cpu_seconds)
+                if out.get("eval"):
+                    out["eval"]["cpu_baseline"] = eval_cpu_baseline(trainer, data)
+        if watchdog is not None:
+            watchdog.beat("cpu baseline")
+        if dist is not None:
+            dist.barrier()
+            if watchdog is not None:
+                watchdog.beat("after baseline barrier")
+            if not args.no_eval:
+                try:
+                    ev = eval_throughput_sharded(trainer, data, dist, rank, world)      # every rank takes part
+                except Exception as e:                # (never lose the training line to the evaluation leg)
+                    ev = {"error": f"{type(e).__name__}: {e}"}
+                if rank == 0:
+                    out["eval"] = ev
+            dist.barrier()
+            dist.destroy_process_group()
+
+    elif dist is not None:
         dist.barrier()
         dist.destroy_process_group()
     if watchdog is not None:

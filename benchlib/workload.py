@@ -30,7 +30,45 @@ def parse(argv=None):
     ap.add_argument("--no-eval", action="store_true")
     ap.add_argument("--no-dropin", action="store_true")
     ap.add_argument("--seed", type=int, default=2024)
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="also the companion measurements: roofline probes, steady state, split16, the N > 1 sub-records, "
+                         "eval, drop-in tiers, CPU baselines (a plain run times the headline steps only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what their last step left a caller (tables, losses) as DIR/<name>.npy")
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
+
+
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, trainer, losses, write=True):
+    """--dump-outputs: what a caller of the timed path holds after its last step -- the trained user / item tables (f32, the
+    real columns) and that step's losses (bpr, reg, cl; f64) -- as <name>.npy, so that two builds can be compared output for
+    output (same arguments: same graph, initial tables, batches and perturbation).  Tables larger than the 64 MB budget are
+    written as a fixed, seeded sample of rows, with the sampled row ids beside them (<name>_rows.npy, f64).  The table views
+    are collectives when tables are sharded: every rank calls, the caller says which one writes.  Returns {name: shape}."""
+    tables = {"user_emb": trainer.user_emb, "item_emb": trainer.item_emb}
+    tables = {k: v.detach().float().cpu().numpy() for k, v in tables.items()}
+    if not write:
+        return None
+    arrays = {"final_losses": np.asarray(losses, dtype=np.float64)}
+    total = sum(a.nbytes for a in tables.values())
+    budget = DUMP_BYTES - (1 << 20)                  # (room for the losses and the row ids)
+    for name, t in tables.items():
+        if total > budget:
+            row_bytes = t.shape[1] * t.itemsize
+            keep = max(1, int(t.shape[0] * budget / total * row_bytes / (row_bytes + 8)))
+            rows = np.sort(np.random.default_rng(0).choice(t.shape[0], size=keep, replace=False))
+            arrays[f"{name}_rows"] = rows.astype(np.float64)
+            t = t[rows]
+        arrays[name] = np.ascontiguousarray(t, dtype=np.float32)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+    return {name: list(a.shape) for name, a in arrays.items()}
 
 
 def build_data(shape, seed):

@@ -291,7 +291,7 @@ def test_bench_gpus_n_launches_itself_under_torchrun():
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
     env.update(SRH_DIST_BACKEND="gloo", OMP_NUM_THREADS="1")
-    p = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1"],
+    p = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--full"],
                        env=env, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]
     line = [ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1]
@@ -408,6 +408,51 @@ def test_bench_runner_counts_epoch_boundaries_and_takes_the_max_over_ranks():
         return Stub(fail=not eager)
     tr, runner, note = bench.first_steps_guarded(make, lambda t: NoFence(t, 7), None, "layout dp")
     assert built == [False, True] and tr.steps == 2 and "RuntimeError" in note
+
+
+def test_bench_dump_outputs_writes_the_last_steps_tables_and_losses(tmp_path, monkeypatch):
+    """`bench.py --dump-outputs DIR`: the tables and losses a caller of the timed path holds after its last step, as f32 /
+    f64 .npy files; tables over the size budget become a seeded sample of rows (the same rows every run, their ids beside
+    them); a rank that does not write still takes part (the table views are collectives under sharding).  And the flags:
+    plain by default, --steps >= 1."""
+    import sys
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    import bench
+    from benchlib import workload
+
+    class Stub:
+        user_emb = torch.arange(40 * 8, dtype=torch.float32).reshape(40, 8) / 7
+        item_emb = -torch.arange(50 * 8, dtype=torch.float32).reshape(50, 8) / 3
+
+    losses = (0.6931, 1.5e-06, 0.98)
+    shapes = bench.dump_outputs(str(tmp_path / "a"), Stub(), losses)
+    assert shapes == {"final_losses": [3], "user_emb": [40, 8], "item_emb": [50, 8]}
+    got = {n: np.load(tmp_path / "a" / f"{n}.npy") for n in shapes}
+    assert got["user_emb"].dtype == np.float32 and np.array_equal(got["user_emb"], Stub.user_emb.numpy())
+    assert got["item_emb"].dtype == np.float32 and np.array_equal(got["item_emb"], Stub.item_emb.numpy())
+    assert got["final_losses"].dtype == np.float64 and got["final_losses"].tolist() == list(losses)
+    assert bench.dump_outputs(str(tmp_path / "b"), Stub(), losses, write=False) is None and not (tmp_path / "b").exists()
+
+    monkeypatch.setattr(workload, "DUMP_BYTES", (1 << 20) + 600)          # a budget of 600 bytes for the tables
+    runs = []
+    for d in ("c", "d"):
+        shapes = bench.dump_outputs(str(tmp_path / d), Stub(), losses)
+        runs.append({n: np.load(tmp_path / d / f"{n}.npy") for n in shapes})
+    assert sorted(runs[0]) == ["final_losses", "item_emb", "item_emb_rows", "user_emb", "user_emb_rows"]
+    assert all(np.array_equal(runs[0][n], runs[1][n]) for n in runs[0])
+    size = 0
+    for name, full in (("user_emb", Stub.user_emb.numpy()), ("item_emb", Stub.item_emb.numpy())):
+        rows = runs[0][f"{name}_rows"]
+        assert rows.dtype == np.float64 and rows.size >= 1 and np.all(np.diff(rows) > 0)
+        assert np.array_equal(runs[0][name], full[rows.astype(np.int64)])
+        size += runs[0][name].nbytes + rows.nbytes
+    assert size <= 600
+
+    args = bench.parse([])
+    assert not args.full and args.dump_outputs is None
+    for bad in (["--steps", "0"], ["--warmup", "-1"]):
+        with pytest.raises(SystemExit):
+            bench.parse(bad)
 
 
 @pytest.mark.parametrize("model,d", [("XSimGCL", 50), ("SGL", 96), ("LightGCN", 20), ("SimGCL", 100)])

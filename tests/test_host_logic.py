@@ -128,17 +128,45 @@ def test_synthetic_generator_invariants():
     assert np.array_equal(tu, tu2)
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/model/graph"), reason="reference checkout not present")
-def test_reference_model_files_import_against_the_mirrors():
-    """dropin.install(): the reference's unmodified model files resolve base.* / util.* / data.* to
-    this package (construction needs a GPU; resolution does not)."""
+def _reference_model_files():
+    """tests/golden/reference_model_files.json (tests/golden/make_fusable_digests.py --json): per model file the engine
+    fuses, the two digests of the reference's file, the modules and names it imports and the bases of its model class."""
+    import json
+    from tests.conftest import GOLDEN
+    with open(os.path.join(GOLDEN, "reference_model_files.json")) as f:
+        return json.load(f)
+
+
+def _stage_model_files(root):
+    """root/model/graph/<Name>.py for each of those files: the reference file's own import statements and its model class
+    on the same bases -- its import surface, written out from the recorded facts; the class body is this test's own.
+    Returns {name: source bytes}."""
+    written = {}
+    for d in (root / "model", root / "model" / "graph"):
+        d.mkdir(parents=True, exist_ok=True)
+        (d / "__init__.py").write_text("")
+    for name, facts in _reference_model_files().items():
+        lines = [f"from {imp['from']} import {', '.join(imp['names'])}" if "from" in imp
+                 else f"import {imp['import']}" + (f" as {imp['as']}" if imp["as"] else "") for imp in facts["imports"]]
+        lines += ["", "", f"class {name}({', '.join(facts['bases'])}):", "    def train(self):",
+                  f"        return {name!r}", ""]
+        written[name] = "\n".join(lines).encode()
+        (root / "model" / "graph" / f"{name}.py").write_bytes(written[name])
+    return written
+
+
+def test_reference_model_files_import_against_the_mirrors(tmp_path):
+    """dropin.install(): model files that import what the reference's unmodified model files import (the recorded
+    import statements, tests/golden/reference_model_files.json) resolve base.* / util.* / data.* to this package
+    (construction needs a GPU; resolution does not)."""
     import importlib
     import sys
     from selfrec_amd import dropin
+    _stage_model_files(tmp_path)
     saved = {k: v for k, v in sys.modules.items() if k.split(".")[0] in ("base", "data", "util", "model")}
     sys.dont_write_bytecode = True
     dropin.install()
-    sys.path.insert(0, "/root/reference")
+    sys.path.insert(0, str(tmp_path))
     try:
         for name in ("MF", "LightGCN", "XSimGCL", "SimGCL", "SGL"):
             mod = importlib.import_module(f"model.graph.{name}")
@@ -147,7 +175,7 @@ def test_reference_model_files_import_against_the_mirrors():
             assert mod.next_batch_pairwise.__module__ == "selfrec_amd.util.sampler"
             assert mod.bpr_loss.__module__ == "selfrec_amd.util.loss_torch"
     finally:
-        sys.path.remove("/root/reference")
+        sys.path.remove(str(tmp_path))
         for k in [k for k in sys.modules if k.split(".")[0] in ("base", "data", "util", "model")]:
             del sys.modules[k]
         sys.modules.update(saved)
@@ -396,28 +424,24 @@ def test_loss_mirrors_evaluate_the_reference_expression_off_the_device(golden_op
 
 def test_fused_dropin_recognises_only_the_unmodified_reference_files(tmp_path, monkeypatch, capsys):
     """dropin.install(fuse=True): a model class gets the fused engine's train() iff its module is model.graph.<Name> and
-    the file is the reference's -- by the SHA-256 of its bytes or of its syntax tree (comments and formatting aside); one
-    edited STATEMENT keeps the file's own train(), and stderr says so.  The
-    reference checkout exists in the build container only -- skipped elsewhere (the GPU-side run of the fused route is
-    tools/run_reference_models.py --fuse on a staged copy)."""
+    the file is the one dropin.FUSABLE names -- by the SHA-256 of its bytes or of its syntax tree (comments and formatting
+    aside); one edited STATEMENT keeps the file's own train(), and stderr says so.
+    The files are staged from the reference's recorded import surface, and FUSABLE holds THEIR digests here; that FUSABLE
+    holds the reference's own is test_fused_dropin_recognises_the_reference_files_by_their_code_not_their_bytes (the
+    GPU-side run of the fused route on the reference's files is tools/run_reference_models.py --fuse on a staged copy)."""
+    import hashlib
     import importlib
-    import shutil
     import sys
-    ref = "/root/reference/model/graph"
-    if not os.path.isfile(os.path.join(ref, "XSimGCL.py")):
-        pytest.skip("no reference checkout here")
     from selfrec_amd import dropin
     from selfrec_amd.model.graph._fused import fused_train_of_reference_class
     stage = tmp_path / "stage"
-    (stage / "model" / "graph").mkdir(parents=True)
-    for name in dropin.FUSABLE:
-        shutil.copy(os.path.join(ref, f"{name}.py"), stage / "model" / "graph" / f"{name}.py")
+    staged = _stage_model_files(stage)
+    monkeypatch.setattr(dropin, "FUSABLE", {name: (hashlib.sha256(src).hexdigest(), dropin.syntax_digest(src.decode()))
+                                            for name, src in staged.items()})
     with open(stage / "model" / "graph" / "SimGCL.py", "a") as f:          # an edited file: one more STATEMENT
         f.write("\nLOCAL_CHANGE = 1\n")
     with open(stage / "model" / "graph" / "SGL.py", "a") as f:             # a comment and blank lines: still the reference's code
         f.write("\n\n# re-formatted upstream\n")
-    for d in (stage / "model", stage / "model" / "graph"):
-        (d / "__init__.py").write_text("")
     monkeypatch.syspath_prepend(str(stage))
     saved = {k: v for k, v in sys.modules.items() if k.split(".")[0] in ("base", "data", "util", "model")}
     for k in saved:
@@ -607,10 +631,15 @@ def test_fused_dropin_recognises_the_reference_files_by_their_code_not_their_byt
     # the table holds both digests for the five files the engine serves
     assert set(dropin.FUSABLE) == {"XSimGCL", "LightGCN", "SimGCL", "SGL", "MF"}
     assert all(len(v) == 2 and all(len(h) == 64 for h in v) for v in dropin.FUSABLE.values())
-    ref = "/root/reference/model/graph"
-    if os.path.isdir(ref):                      # (the build container: the digests ARE the reference's)
-        import hashlib
-        for name, (raw_sha, syn_sha) in dropin.FUSABLE.items():
-            src = open(os.path.join(ref, name + ".py"), "rb").read()
-            assert hashlib.sha256(src).hexdigest() == raw_sha and dropin.syntax_digest(src.decode()) == syn_sha
-            assert dropin.syntax_digest("# re-formatted upstream\n" + src.decode().replace("\n\n", "\n\n\n")) == syn_sha
+    # the digests ARE the reference's: both of each file, as tests/golden/make_fusable_digests.py recorded them from it
+    ref = _reference_model_files()
+    assert set(ref) == set(dropin.FUSABLE)
+    for name, (raw_sha, syn_sha) in dropin.FUSABLE.items():
+        assert (raw_sha, syn_sha) == (ref[name]["sha256"], ref[name]["syntax_sha256"]), name
+    # a re-formatted whole model file keeps its syntax digest (this package's model files stand in for the reference's)
+    graph = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "selfrec_amd", "model", "graph")
+    for fn in sorted(os.listdir(graph)):
+        if fn.endswith(".py") and os.path.getsize(os.path.join(graph, fn)):
+            src = open(os.path.join(graph, fn)).read()
+            reformatted = "# re-formatted upstream\n" + src.replace("\n\n", "\n\n\n")
+            assert dropin.syntax_digest(reformatted) == dropin.syntax_digest(src), fn

@@ -177,29 +177,29 @@ refmodelsfuse)
 precision)
   timeout 900 python tools/precision_probe.py > $OUT/precision_probe.log 2>&1; echo "precision exit $?"; grep -v amdgpu.ids $OUT/precision_probe.log | tail -8;;
 bench)
-  timeout 1200 python bench.py --steps ${BENCH_STEPS:-1300} --warmup 50 > $OUT/bench.log 2> $OUT/bench.err; echo "bench exit $?"
+  timeout 1200 python bench.py --full --steps ${BENCH_STEPS:-1300} --warmup 50 > $OUT/bench.log 2> $OUT/bench.err; echo "bench exit $?"
   tail -3 $OUT/bench.err; tail -1 $OUT/bench.log | cut -c1-3000;;
 benchworld2)
   # every line of bench.py's N > 1 path with N > 1 real ranks -- on ONE GPU, over gloo (figures meaningless)
   for lay in ${W2_LAYOUTS:-auto}; do
     # (auto: the headline = fixed-batch partition, then the dp sub-record; W2_LAYOUTS="auto rows" to force others first)
-    SRH_DIST_BACKEND=gloo:device SRH_SHARD_LAYOUT=$lay timeout 900 python bench.py --gpus ${W2_RANKS:-2} --steps ${W2_STEPS:-100} --warmup 10 --no-cpu-baseline > $OUT/bench_world2_$lay.log 2> $OUT/bench_world2_$lay.err
+    SRH_DIST_BACKEND=gloo:device SRH_SHARD_LAYOUT=$lay timeout 900 python bench.py --gpus ${W2_RANKS:-2} --steps ${W2_STEPS:-100} --warmup 10 --no-cpu-baseline --full > $OUT/bench_world2_$lay.log 2> $OUT/bench_world2_$lay.err
     echo "benchworld2 $lay exit $?"; grep -v "Gloo\|socket.cpp\|amdgpu.ids" $OUT/bench_world2_$lay.err | tail -5; tail -1 $OUT/bench_world2_$lay.log | cut -c1-1500
   done;;
 benchdriver)
-  # what the driver runs: default flags
-  timeout 1200 python bench.py > $OUT/bench_default.log 2> $OUT/bench_default.err; echo "benchdriver exit $?"
+  # the full line at default flags
+  timeout 1200 python bench.py --full > $OUT/bench_default.log 2> $OUT/bench_default.err; echo "benchdriver exit $?"
   tail -3 $OUT/bench_default.err; tail -1 $OUT/bench_default.log | cut -c1-600;;
 benchbig)
   # BASELINE.json configs[3] at N = 1: the full line with roofline + traffic (profiles/spmm_dense_traffic_1m-500k_d128.json)
-  timeout 1200 python bench.py --shape 1m-500k --emb 128 --steps 40 --warmup 5 > $OUT/bench_1m500k.log 2> $OUT/bench_1m500k.err; echo "benchbig exit $?"
+  timeout 1200 python bench.py --full --shape 1m-500k --emb 128 --steps 40 --warmup 5 > $OUT/bench_1m500k.log 2> $OUT/bench_1m500k.err; echo "benchbig exit $?"
   tail -3 $OUT/bench_1m500k.err; tail -1 $OUT/bench_1m500k.log | cut -c1-2500;;
 benchquick)
-  timeout 600 python bench.py --steps 600 --warmup 30 --no-cpu-baseline --no-eval --no-dropin > $OUT/benchquick.log 2> $OUT/benchquick.err; echo "benchquick exit $?"
+  timeout 600 python bench.py --full --steps 600 --warmup 30 --no-cpu-baseline --no-eval --no-dropin > $OUT/benchquick.log 2> $OUT/benchquick.err; echo "benchquick exit $?"
   tail -3 $OUT/benchquick.err; tail -1 $OUT/benchquick.log | cut -c1-1500;;
 benchab)
   for flag in "" "--no-overlap"; do
-    timeout 600 python bench.py --steps 1300 --warmup 30 --no-cpu-baseline --no-eval --no-dropin $flag > $OUT/benchab.log 2> $OUT/benchab.err; echo "benchab [$flag] exit $?"
+    timeout 600 python bench.py --full --steps 1300 --warmup 30 --no-cpu-baseline --no-eval --no-dropin $flag > $OUT/benchab.log 2> $OUT/benchab.err; echo "benchab [$flag] exit $?"
     python -c "import json,sys; d=json.loads(open('$OUT/benchab.log').read().strip().splitlines()[-1]); print(d['ms_per_step'], d['steady_state']['ms_per_step'], d['value'])"
   done;;
 refedited)
@@ -221,11 +221,11 @@ refprof)
   grep -v "amdgpu.ids\|^training" $OUT/refprof.log | cut -c1-230 | tail -80;;
 prof)
   # per-kernel times of the captured step (hipGraph replay), the command bench.py times
-  rm -rf $OUT/prof; (cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats -d $OLDPWD/$OUT/prof -o trace -- python $OLDPWD/bench.py --steps 600 --warmup 50 --no-cpu-baseline --no-eval --no-dropin > $OLDPWD/$OUT/prof.log 2>&1); echo "prof exit $?"
+  rm -rf $OUT/prof; (cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats -d $OLDPWD/$OUT/prof -o trace -- python $OLDPWD/bench.py --full --steps 600 --warmup 50 --no-cpu-baseline --no-eval --no-dropin > $OLDPWD/$OUT/prof.log 2>&1); echo "prof exit $?"
   stats $OUT/prof > $OUT/prof_kernel_stats.txt && head -20 $OUT/prof_kernel_stats.txt; tail -1 $OUT/prof.log | cut -c1-300
   find $OUT/prof -name "*.db" -size +40M -delete;;
 profeval)
-  rm -rf $OUT/profeval; (cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats -d $OLDPWD/$OUT/profeval -o trace -- python $OLDPWD/bench.py --steps ${PROFEVAL_STEPS:-5} --warmup 2 --no-cpu-baseline --no-dropin > $OLDPWD/$OUT/profeval.log 2>&1); echo "profeval exit $?"
+  rm -rf $OUT/profeval; (cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats -d $OLDPWD/$OUT/profeval -o trace -- python $OLDPWD/bench.py --full --steps ${PROFEVAL_STEPS:-5} --warmup 2 --no-cpu-baseline --no-dropin > $OLDPWD/$OUT/profeval.log 2>&1); echo "profeval exit $?"
   stats $OUT/profeval | grep -E "kernel  |gemm_nt|filter16|rescore|topk|mask_kernel|split_rows|metric_rows|cand_|hit_flags" > $OUT/profeval_kernel_stats.txt; cat $OUT/profeval_kernel_stats.txt
   find $OUT/profeval -name "*.db" -size +40M -delete;;
 pmc)
@@ -254,7 +254,7 @@ cols)
   COLS_PROBE_KERNELS_ONLY=${COLS_PROBE_KERNELS_ONLY:-0} timeout 900 python tools/cols_probe.py > $OUT/cols_probe.log 2>&1; echo "cols exit $?"; grep -v amdgpu.ids $OUT/cols_probe.log | tail -30;;
 sharded1)
   for lay in ${SHARDED1_LAYOUTS:-rows cols dp}; do
-    SRH_FORCE_SHARDED=1 SRH_SHARD_LAYOUT=$lay timeout 600 python bench.py --steps 300 --warmup 20 --no-cpu-baseline > $OUT/bench_sharded1_$lay.log 2> $OUT/bench_sharded1_$lay.err; echo "sharded1 $lay exit $?"
+    SRH_FORCE_SHARDED=1 SRH_SHARD_LAYOUT=$lay timeout 600 python bench.py --full --steps 300 --warmup 20 --no-cpu-baseline > $OUT/bench_sharded1_$lay.log 2> $OUT/bench_sharded1_$lay.err; echo "sharded1 $lay exit $?"
     tail -2 $OUT/bench_sharded1_$lay.err; tail -1 $OUT/bench_sharded1_$lay.log | cut -c1-500
   done;;
 modelmatrix)
@@ -270,7 +270,7 @@ benchdriver20)
   timeout 1200 python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_driver20.log 2> $OUT/bench_driver20.err; echo "benchdriver20 exit $?"
   tail -3 $OUT/bench_driver20.err; tail -1 $OUT/bench_driver20.log | cut -c1-900;;
 ablibs)
-  bash tools/spmm_lab/ab_libs.sh ${AB_LIBS:-} 2>&1 | grep -v amdgpu.ids | tee $OUT/ab_libs.txt | cut -c1-420;;
+  OUT=$OUT bash tools/spmm_lab/ab_libs.sh ${AB_LIBS:-} 2>&1 | grep -v amdgpu.ids | tee $OUT/ab_libs.txt | cut -c1-420;;
 abtest)
   # kernel + engine parity tests under an alt library (AB_TEST_LIBS), the product's restored afterwards
   cp selfrec_amd/lib/libselfrec_hip.so /tmp/orig_t.so
