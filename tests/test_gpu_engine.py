@@ -13,6 +13,7 @@ from selfrec_amd.data.ui_graph import Interaction
 from selfrec_amd.engine import FusedTrainer
 
 from .conftest import EDGE_TAGS
+from .counter_rng import EngineNoise
 
 pytestmark = pytest.mark.gpu
 MODELS = ["MF", "LightGCN", "XSimGCL", "SimGCL", "SGL"]
@@ -545,6 +546,70 @@ def test_other_embedding_sizes_match_oracle(name, d):
     diff = np.abs(got - want)
     assert diff.max() < 5e-5 and (diff > 3e-6).mean() < 1e-3
     assert rel_err(got, want) < 5e-4
+
+
+# (model, embedding.size, layers, extra trainer kw): the benchmark's XSimGCL (bench.py: L = 3, l* = 1, eps = lambda = tau
+# = 0.2, d = 64), SimGCL's shared first layer (FANOUT with two extra counter offsets), zero-padded rows, d = 128, and a
+# depth whose 2L perturbed calls exceed the 16 the counter stride reserves at least, and a run resumed at an optimiser step
+# where step * stride crosses 2^32 (the high word of the counter; the 1 M x 500 k shape gets there after 180 steps)
+TIMED_CASES = [("XSimGCL", 64, 3, {}), ("SimGCL", 64, 3, {"rng_seed": 0x3C5A_0001_5E1F_0EC}), ("XSimGCL", 50, 3, {}),
+               ("XSimGCL", 128, 3, {}), ("XSimGCL", 64, 9, {}), ("XSimGCL", 64, 3, {"start_step": 335_542})]
+
+
+@pytest.mark.parametrize("name,d,L,over", TIMED_CASES, ids=[f"{c[0]}-d{c[1]}-L{c[2]}" for c in TIMED_CASES])
+def test_captured_step_with_in_kernel_noise_matches_oracle(name, d, L, over):
+    """The configuration bench.py times -- captured steps (use_graph=True), the noise drawn IN KERNEL (noise_fn=None), fused
+    Adam, det_scatter, f32 InfoNCE -- against the CPU oracle fed the same numbers by the host restatement of the counter
+    RNG (tests/counter_rng.py), step by step over one epoch and two steps of the next (cursor[1] crosses the boundary).
+    Power check: an oracle fed the previous step's noise (SimGCL: views a and b swapped) must NOT meet the loss bound."""
+    tu, ti, su, si, U, I = synth.make_dataset("tiny")
+    data = Interaction({}, synth.as_triples(tu, ti), [])
+    torch.manual_seed(11)
+    ue = torch.nn.init.xavier_uniform_(torch.empty(U, d)); ie = torch.nn.init.xavier_uniform_(torch.empty(I, d))
+    B = 1500
+    kw = dict(n_layers=L, lr=1e-3, reg=1e-4, cl_rate=0.2, eps=0.2, tau=0.2, layer_cl=1, batch_size=B)
+    over = dict(over)
+    step = over.pop("start_step", 1) - 1
+    tr = FusedTrainer(data, d, model=name, user_emb=ue, item_emb=ie, noise_fn=None, use_graph=True, nce_precision="f32",
+                      **kw, **over)
+    assert tr.use_graph and tr.fuse_adam and tr.det_scatter and tr._rng_calls == max(16, 2 * L)
+    noise = EngineNoise(tr)
+    wrong = EngineNoise(tr, swap_views=True) if name == "SimGCL" else EngineNoise(tr, lag=1)
+    ref, ref_wrong = (O.OracleTrainer(name, data.train_u, data.train_i, U, I, d, user_emb=ue, item_emb=ie, noise_fn=f, **kw)
+                      for f in (noise, wrong))
+    if step:
+        # resume at optimiser step `step + 1`: the cursor and both optimisers' step counts (Adam's moments start at zero)
+        tr.cursor[1] = step + 1
+        for r in (ref, ref_wrong):
+            for p in (r.user_emb, r.item_emb):
+                r.opt.state[p] = {"step": torch.tensor(float(step)), "exp_avg": torch.zeros_like(p),
+                                  "exp_avg_sq": torch.zeros_like(p)}
+        assert (step + 1) * tr.P * tr._rng_calls < 1 << 32 < (step + 6) * tr.P * tr._rng_calls
+    first = step + 1
+    random.seed(29)
+    tr.seed_sampler_from_python()
+    off_bound = 0
+    for epoch in range(2):
+        nb = tr.begin_epoch()
+        eu, ei, ej = tr.epoch_node_ids()
+        for b in range(nb if epoch == 0 else 2):
+            step += 1
+            assert int(tr.cursor[1]) == step                    # the optimiser step the launches read their counters at
+            tr.step()
+            got = tr.read_losses()
+            lo, hi = b * B, min((b + 1) * B, len(eu))
+            batch = (eu[lo:hi].tolist(), ei[lo:hi].tolist(), ej[lo:hi].tolist())
+            noise.step = wrong.step = step
+            want = ref.step(*batch)
+            np.testing.assert_allclose(got, want, rtol=3e-5, atol=1e-9, err_msg=f"step {step}")
+            w = ref_wrong.step(*batch)
+            off_bound += not np.allclose(got, w, rtol=3e-5, atol=1e-9)
+    assert step - first >= 4 and tr._graph is not None
+    assert off_bound > 0, "the oracle met the bound with the wrong noise: the comparison has no power"
+    got = np.concatenate([tr.user_emb.cpu().numpy(), tr.item_emb.cpu().numpy()])
+    want = np.concatenate([ref.user_emb.detach().numpy(), ref.item_emb.detach().numpy()])
+    diff = np.abs(got - want)
+    assert diff.max() < 5e-5 and (diff > 3e-6).mean() < 1e-3, (diff.max(), (diff > 3e-6).mean())
 
 
 @pytest.mark.parametrize("name,L,l_star", [("XSimGCL", 1, 0), ("XSimGCL", 1, 1), ("XSimGCL", 4, 0), ("XSimGCL", 4, 4),

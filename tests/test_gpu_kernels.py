@@ -12,6 +12,8 @@ import torch
 from oracle import selfrec_oracle as O
 from selfrec_amd import ops
 
+from .counter_rng import counter_noise
+
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
 
@@ -277,6 +279,167 @@ def test_spmm_rng_perturbation_properties():
                                                      rng_step=step, rng_stride=n))
     f = ops.spmm(csr, tx, epilogue=ops.make_epilogue(perturb_eps=0.2, rng_seed=7, rng_offset=3 * n))
     assert torch.equal(e, f)
+
+
+# ---- the in-kernel counter noise, number for number (tests/counter_rng.py restates the mixer on the host)
+RNG_SEED = 0xA5C3_0F17_5E1F_0EC9          # a high word that is not zero
+RNG_EPS = 0.2
+
+
+def _counter_modes(n):
+    """(name, rng_offset, device step, stride, n_extra, main_clean, row-masked) of the launches every case runs"""
+    stride = 16 * n
+    near62 = ((1 << 62) - 3 * stride) // stride            # step * stride crosses 2^32 and sits just under 2^62
+    return [("plain", 0, None, 0, 0, False, False),
+            ("offset_crosses_2^32", (1 << 32) - n // 2, None, 0, 0, False, False),
+            ("device_step_near_2^62", 5 * n + 3, near62, stride, 0, False, False),
+            ("fanout_main_perturbed", (1 << 32) - 7, 3, stride, 2, False, False),
+            ("fanout_main_clean", 11, near62 + 1, stride, 2, True, False),
+            ("row_masked", 2 * n, 9, stride, 0, False, True)]
+
+
+def _check_counter_launch(csr, m64, x, d_full, col0, d_valid, *, pattern=False, row_scale=None, tol=2e-6):
+    """Each counter mode: the counter launch == the launch with the restated noise injected (bit for bit on the rows /
+    slice kernels, 2e-6 relative on the pair kernel: its injected path sums the norm in another order), both within tol
+    of float64 y + sign(y) eps u / ||u|| (u: the restatement, norm over the whole row's valid columns), padding exactly 0,
+    unmarked rows untouched."""
+    n, d = m64.shape[0], x.shape[1]
+    dv = d_full if d_valid is None else d_valid
+    tx = torch.from_numpy(x).to(DEV)
+    y64 = m64 @ x.astype(np.float64)
+    if row_scale is not None:
+        y64 = y64 * row_scale.astype(np.float64)[:, None]
+    slice_kw = dict(d_full=d_full, col0=col0) if d_full != d else {}
+    if d_valid is not None:
+        slice_kw["d_valid"] = d_valid
+    scale_kw = dict(row_scale=torch.from_numpy(row_scale).to(DEV), scale_in=True) if row_scale is not None else {}
+    exact = d != 8
+    for name, off, step, stride, n_extra, main_clean, masked in _counter_modes(n):
+        extra_off = [off + (k + 1) * n for k in range(n_extra)]
+        step_t = torch.tensor([step], dtype=torch.int64, device=DEV) if step is not None else None
+        mark_kw, live = {}, np.ones(n, dtype=bool)
+        if masked:
+            live = np.random.default_rng(n + d).random(n) < 0.4
+            mark = torch.from_numpy(np.where(live, 17, 16).astype(np.int32)).to(DEV)
+            mark_kw = dict(row_mark=mark, mark_stamp=torch.tensor([17], dtype=torch.int64, device=DEV))
+
+        def restated(o):
+            c0 = (o + (step or 0) * stride) & 0xFFFFFFFFFFFFFFFF
+            return counter_noise(RNG_SEED, c0, n, d_full, d_valid)
+
+        noises = [restated(o) for o in [off] + extra_off]
+        runs = []
+        for inject in (False, True):
+            outs = [torch.full((n, d), 7.0, device=DEV) for _ in range(1 + n_extra)]
+            kw = dict(perturb_eps=RNG_EPS, rng_seed=RNG_SEED, rng_offset=off, rng_step=step_t, rng_stride=stride)
+            if inject:
+                # (injected noise is whole rows: (n, d_full) under a slice, (n, d) otherwise; the counter fields are ignored)
+                kw.update(noise=torch.from_numpy(noises[0]).to(DEV), rng_step=None)
+            if n_extra:
+                kw.update(extra_out=outs[1:], extra_rng_offset=extra_off, main_clean=main_clean,
+                          extra_noise=[torch.from_numpy(z).to(DEV) for z in noises[1:]] if inject else None)
+            ops.spmm(csr, tx, out=outs[0], pattern=pattern,
+                     epilogue=ops.make_epilogue(**kw, **slice_kw, **scale_kw, **mark_kw))
+            runs.append([o.cpu().numpy() for o in outs])
+        for k, (got, inj) in enumerate(zip(*runs)):
+            what = f"{name} output {k} (d={d} of {d_full}, col0={col0}, d_valid={d_valid})"
+            if exact:
+                assert np.array_equal(got, inj), what
+            else:
+                assert rel_err(got, inj) < 2e-6, what
+            clean = k == 0 and main_clean
+            u = noises[0 if clean else k].astype(np.float64)
+            pert = np.sign(y64) * RNG_EPS * (u / np.linalg.norm(u, axis=1, keepdims=True))[:, col0:col0 + d]
+            want = y64 if clean else y64 + pert
+            assert np.all(got[~live] == 7.0) and np.all(inj[~live] == 7.0), what        # unmarked rows left alone
+            ambiguous = (np.abs(y64) < 1e-6) & (y64 != 0)                               # sign(y) not decided in fp32
+            assert ambiguous.sum() <= 4 + 1e-4 * ambiguous.size, what
+            sel = live[:, None] & ~ambiguous
+            for t in (got, inj):
+                assert np.abs(t - want)[sel].max() <= tol * np.abs(want).max(), what
+                assert np.all(t[live][y64[live] == 0] == 0), what                      # sign(0) = 0: no move
+            if d_valid is not None and col0 + d > d_valid:
+                assert np.all(got[live][:, max(d_valid - col0, 0):] == 0), what          # padding columns stay exactly 0
+
+
+def _counter_graph(n_rows=3000, n_cols=2500):
+    m = powerlaw_csr(n_rows, n_cols, 40000, seed=23, heavy_rows=3, heavy_len=1500, empty_rows=40)
+    # split_len = 64: the heavy rows finish through the coop / partial-sum path
+    return m, m.astype(np.float64), ops.DeviceCSR.from_scipy(m, split_len=64)
+
+
+def _counter_x(n_cols, d, col0, d_valid, seed):
+    x = np.random.default_rng(seed).standard_normal((n_cols, d)).astype(np.float32)
+    x[:, 1] = 0.0                                            # exact zeros in y: the sign(0) branch
+    if d_valid is not None:
+        x[:, max(d_valid - col0, 0):] = 0.0                  # the padding columns of the whole row are zero
+    return x
+
+
+def _spmm_path(d):
+    return "pair" if d == 8 else "slice" if d <= 32 else "rows"
+
+
+# (slice width d, whole-row width d_full, d_valid or None): whole rows, column slices, zero-padded rows, padded slices
+COUNTER_CASES = [(64, 64, None), (128, 128, None), (256, 256, None), (32, 32, None),
+                 (16, 64, None), (32, 64, None), (32, 128, None), (64, 128, None), (64, 256, None), (128, 256, None),
+                 (8, 32, None), (8, 64, None),
+                 (64, 64, 50), (128, 128, 100), (256, 256, 200),
+                 (64, 128, 100), (128, 256, 200)]
+
+
+@pytest.mark.parametrize("d,d_full,d_valid", COUNTER_CASES,
+                         ids=[f"{_spmm_path(c[0])}-{c[0]}of{c[1]}" + (f"-valid{c[2]}" if c[2] else "") for c in COUNTER_CASES])
+def test_spmm_counter_noise_equals_host_restatement(d, d_full, d_valid):
+    """Which numbers the epilogue's counter RNG draws (spmm_rows_kernel d = 64 / 128 / 256, spmm_slice_kernel d = 16 / 32,
+    spmm_pair_kernel d = 8 through thin_perturb), at every col0 of the slice, against tests/counter_rng.py: a seed with a
+    high word, a counter offset crossing 2^32 inside the launch, a device step whose step * stride sits near 2^62, FANOUT
+    with two extra offsets (main output perturbed and clean), a row-masked launch."""
+    m, m64, csr = _counter_graph()
+    for col0 in range(0, d_full, d):
+        x = _counter_x(m.shape[1], d, col0, d_valid, seed=col0 + d)
+        _check_counter_launch(csr, m64, x, d_full, col0, d_valid)
+
+
+@pytest.mark.parametrize("d,d_full,d_valid", [(64, 64, None), (128, 128, 100), (64, 128, None)])
+def test_spmm_counter_noise_value_free_row_scaled(d, d_full, d_valid):
+    """The value-free product (pattern=True, row scale applied before the perturbation) draws the same numbers."""
+    m, _, csr = _counter_graph()
+    pat = m.copy()
+    pat.data[:] = 1.0
+    scale = np.random.default_rng(4).uniform(0.05, 1.0, m.shape[0]).astype(np.float32)
+    for col0 in range(0, d_full, d):
+        x = _counter_x(m.shape[1], d, col0, d_valid, seed=col0 + 3)
+        _check_counter_launch(csr, pat.astype(np.float64), x, d_full, col0, d_valid, pattern=True, row_scale=scale)
+
+
+def test_spmm_counter_noise_under_graph_replay_follows_the_device_step():
+    """One SpMM launch captured with the rng_step pointer: replays after writing steps 1, 2, 3 draw the restatement's
+    numbers of that step (the launch has no parallel branches)."""
+    m, m64, csr = _counter_graph()
+    n, d = m.shape[0], 64
+    x = _counter_x(m.shape[1], d, 0, None, seed=1)
+    tx = torch.from_numpy(x).to(DEV)
+    out = torch.zeros((n, d), device=DEV)
+    step = torch.zeros(1, dtype=torch.int64, device=DEV)
+    off, stride = 3 * n, 16 * n
+    ep = ops.make_epilogue(perturb_eps=RNG_EPS, rng_seed=RNG_SEED, rng_offset=off, rng_step=step, rng_stride=stride)
+    ops.spmm(csr, tx, out=out, epilogue=ep)                    # warm-up (module load) outside the capture
+    torch.cuda.synchronize()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        ops.spmm(csr, tx, out=out, epilogue=ep)
+    seen = []
+    for s in (1, 2, 3):
+        step.fill_(s)
+        g.replay()
+        torch.cuda.synchronize()
+        z = torch.from_numpy(counter_noise(RNG_SEED, off + s * stride, n, d)).to(DEV)
+        want = ops.spmm(csr, tx, epilogue=ops.make_epilogue(perturb_eps=RNG_EPS, noise=z))
+        got = out.clone()
+        assert torch.equal(got, want), s
+        seen.append(got)
+    assert not torch.equal(seen[0], seen[1]) and not torch.equal(seen[1], seen[2])
 
 
 def test_value_free_product_with_row_scaling(tiny_data):

@@ -516,3 +516,47 @@ def test_duplicate_interactions_weigh_two_in_adj_and_one_in_views(shapes):
     m.eliminate_zeros(); m.sort_indices()
     assert np.array_equal(m.indices, shapes["dup_drop_lap_indices"])
     assert np.array_equal(m.data, shapes["dup_drop_lap_data"])
+
+
+def test_yelp_shape_timed_step_matches_oracle_with_restated_noise():
+    """The step bench.py times, at its shape: Yelp2018 (benchlib.workload.build_data), XSimGCL L = 3, l* = 1,
+    eps = lambda = tau = 0.2, d = 64, batch 2048, f32 InfoNCE, captured steps with the noise drawn in kernel -- two steps
+    against the CPU oracle fed the same numbers by the host restatement of the counter RNG (tests/counter_rng.py).
+    Losses to 1e-5; parameters: fewer than 0.1 % of the elements more than 3e-6 off (test_gpu_engine.py's bound), and --
+    over the whole 4.5 M-element table, not a sample -- at most 20 elements between 5e-5 and 1e-4 (10 % of one Adam step):
+    the module docstring's Adam amplification of fp32 summation-order noise in the smallest gradients.  Measured: 50 of
+    4,461,824 elements above 3e-6, one above 5e-5 (6.3e-5, where the oracle's gradient RMS is 1.1e-7); most of the rest sit
+    in one column of neighbouring rows -- one perturbed element whose product is ~0 takes sign(h) from the summation order
+    and the next product spreads its jump (PreAdamProbe above).  The oracle takes ~0.45 s per step on 16 CPUs: two steps."""
+    from benchlib.workload import build_data
+    from oracle import selfrec_oracle as O
+    from .counter_rng import EngineNoise
+    seed = 2024                                           # bench.py's --seed default (benchlib/workload.py)
+    data, _ = build_data("yelp2018", seed)
+    # bench.py:168-180 (kw and the trainer it times), restated
+    kw = dict(model="XSimGCL", n_layers=3, lr=1e-3, reg=1e-4, cl_rate=0.2, eps=0.2, tau=0.2, layer_cl=1, batch_size=2048,
+              nce_precision="f32")
+    torch.manual_seed(seed)
+    tr = FusedTrainer(data, 64, use_graph=True, sampler_seed=seed, **kw)
+    assert tr.noise_fn is None and tr.use_graph and tr.fuse_adam and tr.det_scatter
+    ue, ie = tr.user_emb.cpu().clone(), tr.item_emb.cpu().clone()
+    noise = EngineNoise(tr)
+    okw = {k: v for k, v in kw.items() if k not in ("model", "nce_precision")}
+    ref = O.OracleTrainer("XSimGCL", data.train_u, data.train_i, tr.U, tr.I, 64, user_emb=ue, item_emb=ie,
+                          noise_fn=noise, **okw)
+    tr.seed_sampler(seed)
+    tr.begin_epoch()
+    eu, ei, ej = tr.epoch_node_ids()
+    B = kw["batch_size"]
+    for b in range(2):
+        tr.step()
+        got = tr.read_losses()
+        noise.step = b + 1
+        sl = slice(b * B, (b + 1) * B)
+        want = ref.step(eu[sl].tolist(), ei[sl].tolist(), ej[sl].tolist())
+        np.testing.assert_allclose(got, want, rtol=1e-5, atol=1e-9, err_msg=f"step {b + 1}")
+    got = np.concatenate([tr.user_emb.cpu().numpy(), tr.item_emb.cpu().numpy()])
+    want = np.concatenate([ref.user_emb.detach().numpy(), ref.item_emb.detach().numpy()])
+    diff = np.abs(got - want)
+    assert (diff > 3e-6).mean() < 1e-3, (diff > 3e-6).mean()
+    assert diff.max() < 0.1 * kw["lr"] and int((diff >= 5e-5).sum()) <= 20, (diff.max(), int((diff >= 5e-5).sum()))
