@@ -40,7 +40,7 @@ enum {
 };
 
 /* ABI version: bumped whenever a signature or struct below changes. */
-#define SRH_ABI_VERSION 30
+#define SRH_ABI_VERSION 31
 int32_t srh_abi_version(void);
 const char* srh_last_error_string(void);
 /* Number of visible HIP devices (0 when there is none -- never an error). */
@@ -713,6 +713,57 @@ srh_status_t srh_allgather_rows(const float* d_rows /* (n_rows, d) */, float* d_
 srh_status_t srh_reducescatter_rows(const float* d_table /* (world n_rows, d) */, float* d_rows /* (n_rows, d) */,
                                     int64_t n_rows, int32_t d, void* comm, void* stream);
 srh_status_t srh_allreduce_sum_f32(float* d_buf, int64_t n_elem, void* comm, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * (a-12) Batch rows against a whole table: InfoNCE forward + backward -- replaces
+ * model/graph/NCL.py:57-83 ssl_layer_loss (the user side and the item side, one problem each).
+ *
+ *   q_b = normalize(Q_b), t_j = normalize(T_j)              (F.normalize: x / max(|x|, 1e-12))
+ *   loss = sum_b [ -q_b.t_idx[b] / tau + log sum_j exp(q_b.t_j / tau) ]   (a SUM over b)
+ * Q (B x d): the gathered query rows (may repeat); T (N x d): the whole table; idx (B, int32):
+ * the positive row of each query in T (may repeat).  The B x N logits are never materialised;
+ * exponentials are taken as exp((s - 1) / tau) (unit rows: no running max needed).  Both
+ * products of both passes run on the f32 MFMA.  No float atomics: the same bits on every call.
+ * Outputs are WRITTEN: d_loss[0] = loss_scale * loss (double), d_gq (B x d) = loss_scale *
+ * dL/dQ, d_gt (N x d, dense) = loss_scale * dL/dT.  d = 64 or 128 (zero-pad narrower rows).
+ * d_ws >= the SUM over problems of srh_table_nce_ws_bytes(B, N, d).  `problems` is a HOST
+ * array of 1 or 2 problems.
+ * ---------------------------------------------------------------------------------- */
+typedef struct srh_table_nce_problem {
+  const float* d_q;
+  const float* d_t;
+  const int32_t* d_idx;
+  int64_t B;
+  int64_t N;
+  float loss_scale;
+  double* d_loss;
+  float* d_gq;
+  float* d_gt;
+} srh_table_nce_problem_t;
+int64_t srh_table_nce_ws_bytes(int64_t B, int64_t N, int32_t d);
+srh_status_t srh_table_nce_fwd_bwd(const srh_table_nce_problem_t* problems, int32_t n_problems,
+                                   int32_t d, float tau, void* d_ws, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * (a-13) k-means steps on the device -- replace faiss.Kmeans(d, k).train(x) and
+ * kmeans.index.search(x, 1) at model/graph/NCL.py:37-40 (run_kmeans, called by e_step).
+ *
+ * srh_kmeans_assign_f32: for each of the n rows of x (n x d), the nearest of the k centroids
+ *   c (k x d) by |c_j|^2 - 2 x.c_j (f32 MFMA product with the argmin fused, no n x k matrix);
+ *   ties go to the lowest j.  d_out_ids[i] = j, d_out_dist[i] = max(|x_i|^2 + that, 0).
+ *   d = 64 or 128 (zero-pad narrower rows).
+ * srh_kmeans_update_f32: per-cluster means and counts of the rows of x under d_ids (rows whose
+ *   id is outside [0, k) are ignored).  Each cluster sums its rows in ascending row order
+ *   after a stable counting sort, then multiplies by 1/count: the same bits on every call, no
+ *   float atomics.  An empty cluster gets a zero centroid and count 0.  Any d >= 1.
+ *   d_ws >= srh_kmeans_update_ws_bytes(n, k).
+ * ---------------------------------------------------------------------------------- */
+srh_status_t srh_kmeans_assign_f32(const float* d_x, int64_t n, const float* d_c, int64_t k,
+                                   int32_t d, int32_t* d_out_ids, float* d_out_dist, void* stream);
+int64_t srh_kmeans_update_ws_bytes(int64_t n, int64_t k);
+srh_status_t srh_kmeans_update_f32(const float* d_x, int64_t n, const int32_t* d_ids, int64_t k,
+                                   int32_t d, float* d_out_centroids, int32_t* d_out_counts,
+                                   void* d_ws, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * (f-1) Dataset files -> id arrays -- replaces the python loops of data/loader.py:22-33

@@ -14,7 +14,7 @@ import torch  # noqa: F401  (must precede CDLL: see module docstring)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libselfrec_hip.so")
-ABI_VERSION = 30
+ABI_VERSION = 31
 
 SRH_EPI_PERTURB, SRH_EPI_MEAN, SRH_EPI_AXPY, SRH_EPI_ADAM = 1, 2, 4, 8
 SRH_MAX_ADAM_CLEAR = 4
@@ -43,6 +43,12 @@ class InfonceProblem(C.Structure):
     """struct srh_infonce_problem (include/selfrec_hip.h)."""
     _fields_ = [("d_v1", C.c_void_p), ("d_v2", C.c_void_p), ("d_idx", C.c_void_p), ("n", C.c_int64),
                 ("d_n", C.c_void_p), ("d_g1", C.c_void_p), ("d_g2", C.c_void_p), ("g2_exclusive", C.c_int32)]
+
+
+class TableNceProblem(C.Structure):
+    """struct srh_table_nce_problem (include/selfrec_hip.h)."""
+    _fields_ = [("d_q", C.c_void_p), ("d_t", C.c_void_p), ("d_idx", C.c_void_p), ("B", C.c_int64), ("N", C.c_int64),
+                ("loss_scale", C.c_float), ("d_loss", C.c_void_p), ("d_gq", C.c_void_p), ("d_gt", C.c_void_p)]
 
 
 class L2Block(C.Structure):
@@ -150,6 +156,11 @@ SIGNATURES = {
     "srh_infonce_fwd_bwd_multi": (_i32, [C.POINTER(InfonceProblem), _i32, _i32, _f32, _f32, _vp, _vp, _i32, _vp]),
     "srh_bpr_infonce_fwd_bwd": (_i32, [C.POINTER(BprProblem), C.POINTER(InfonceProblem), _i32, _i32, _f32, _f32, _vp, _vp,
                                        _i32, _vp]),
+    "srh_table_nce_ws_bytes": (_i64, [_i64, _i64, _i32]),
+    "srh_table_nce_fwd_bwd": (_i32, [C.POINTER(TableNceProblem), _i32, _i32, _f32, _vp, _vp]),
+    "srh_kmeans_assign_f32": (_i32, [_vp, _i64, _vp, _i64, _i32, _vp, _vp, _vp]),
+    "srh_kmeans_update_ws_bytes": (_i64, [_i64, _i64]),
+    "srh_kmeans_update_f32": (_i32, [_vp, _i64, _vp, _i64, _i32, _vp, _vp, _vp, _vp]),
     "srh_adam_step": (_i32, [_vp, _vp, _vp, _vp, _i64, _i64, _vp, _f32, _f32, _f32, _f32, _vp]),
     "srh_adam_step_reset": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _vp, _f32, _f32, _f32, _f32, _vp, _i32, _vp, _vp, _vp]),
     "srh_score_mask_topk": (_i32, [_vp, _vp, _i64, _vp, _i64, _i32, _vp, _vp, _i32, _vp, _i64, _vp, _vp, _vp]),

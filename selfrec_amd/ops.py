@@ -23,7 +23,7 @@ def gpu_available() -> bool:
 __all__ = ["Sampler", "DeviceCSR", "column_class_order", "spmm", "spmm_any", "pad_cols", "padded_width", "spmm3", "spmm_probe", "spmm_set_xcd_shares", "spmm_plan_run_tasks", "adj_sym_normalize", "bpr_l2_fwd_bwd", "bpr_fwd", "bpr_bwd",
            "sumsq", "set_infonce_precision", "get_infonce_precision", "infonce_fwd_bwd", "infonce_multi", "bpr_infonce", "infonce_ws", "adam_step", "score_mask_topk", "score_mask_topk_filtered", "gemm_nt", "topk_rows", "topk_hit_flags", "metric_rows",
            "axpby", "batch_fetch", "zero_rows", "cursor_advance", "batch_lists", "batch_pack", "batch_unpack", "batch_scatter",
-           "SelfrecHipError"]
+           "table_nce_ws", "table_nce_fwd_bwd", "kmeans_assign", "kmeans_update", "kmeans", "SelfrecHipError"]
 
 
 def _stream() -> int:
@@ -992,3 +992,167 @@ def batch_scatter(lists, pairs, d_full, col0, dl):
     check(_lib.load().srh_batch_scatter(C.byref(lists), len(pairs), _ptr_array([c for c, _ in pairs], "compact_grad"),
                                         _ptr_array([g for _, g in pairs], "local_grad"), int(d_full), int(col0), int(dl),
                                         _stream()), "srh_batch_scatter")
+
+
+# ---- NCL (model/graph/NCL.py): batch rows against a whole table, and the k-means of the E-step ----------------------
+TABLE_NCE_WIDTHS = (64, 128)                 # srh_table_nce_fwd_bwd / srh_kmeans_assign_f32 (narrower rows: zero-padded)
+
+
+def table_nce_ws(problems, d: int, device):
+    """Workspace for srh_table_nce_fwd_bwd: problems = [(B, N), ...]."""
+    lib = _lib.load()
+    need = sum(int(lib.srh_table_nce_ws_bytes(int(b), int(n), int(d))) for b, n in problems)
+    return torch.empty(need, dtype=torch.uint8, device=device)
+
+
+def table_nce_fwd_bwd(problems, *, tau, ws=None):
+    """InfoNCE of batch rows against a whole table, forward and backward in one call (NCL.py:57-83 ssl_layer_loss).
+
+    problems: [(q, t, idx, loss_scale), ...] (one or two; NCL passes the user side and the item side): q (B x d) the
+    gathered query rows, t (N x d) the whole table, idx (B) the positive row of each query in t.  Per problem
+        loss = loss_scale * sum_b [ -q_b.t_idx[b] / tau + log sum_j exp(q_b.t_j / tau) ]   (rows F.normalize'd)
+    Returns [(loss (0-dim float64), dL/dq (B x d), dL/dt (N x d)), ...], the gradients scaled by loss_scale.  Any d up
+    to 128: narrower rows are zero-padded for the kernels, which changes no result."""
+    if not 1 <= len(problems) <= 2:
+        raise SelfrecHipError("table_nce_fwd_bwd: one or two problems per call")
+    d = int(problems[0][0].shape[1])
+    w = padded_width(d, TABLE_NCE_WIDTHS)
+    if w is None:
+        raise SelfrecHipError(f"table_nce_fwd_bwd: rows of {d} columns -- the kernels serve up to {TABLE_NCE_WIDTHS[-1]}")
+    dev = problems[0][0].device
+    arr = (_lib.TableNceProblem * len(problems))()
+    keep, outs, shapes = [], [], []
+    for k, (q, t, idx, scale) in enumerate(problems):
+        if q.dim() != 2 or t.dim() != 2 or int(q.shape[1]) != d or int(t.shape[1]) != d:
+            raise SelfrecHipError("table_nce_fwd_bwd: q and t must be 2-D with the same number of columns")
+        if idx.dim() != 1 or int(idx.shape[0]) != int(q.shape[0]):
+            raise SelfrecHipError("table_nce_fwd_bwd: idx must hold one entry per query row")
+        qp, tp = pad_cols(q.float(), w), pad_cols(t.float(), w)
+        ip = idx.to(torch.int32).contiguous()
+        B, N = int(qp.shape[0]), int(tp.shape[0])
+        loss = torch.empty((), dtype=torch.float64, device=dev)
+        gq = torch.empty((B, w), dtype=torch.float32, device=dev)
+        gt = torch.empty((N, w), dtype=torch.float32, device=dev)
+        arr[k].d_q, arr[k].d_t, arr[k].d_idx = _p(qp, torch.float32, "q"), _p(tp, torch.float32, "t"), _p(ip, torch.int32, "idx")
+        arr[k].B, arr[k].N, arr[k].loss_scale = B, N, float(scale)
+        arr[k].d_loss, arr[k].d_gq, arr[k].d_gt = _p(loss), _p(gq), _p(gt)
+        keep += [qp, tp, ip]
+        outs.append((loss, gq, gt))
+        shapes.append((B, N))
+    need = sum(int(_lib.load().srh_table_nce_ws_bytes(b, n, w)) for b, n in shapes)
+    if ws is None or ws.numel() * ws.element_size() < need:
+        ws = table_nce_ws(shapes, w, dev)
+    check(_lib.load().srh_table_nce_fwd_bwd(arr, len(problems), w, float(tau), _p(ws), _stream()), "srh_table_nce_fwd_bwd")
+    return [(loss, gq[:, :d], gt[:, :d]) for loss, gq, gt in outs]
+
+
+def _km_padded(x, what):
+    d = int(x.shape[1])
+    w = padded_width(d, TABLE_NCE_WIDTHS)
+    if w is None:
+        raise SelfrecHipError(f"{what}: rows of {d} columns -- the kernel serves up to {TABLE_NCE_WIDTHS[-1]}")
+    return pad_cols(x, w)
+
+
+def kmeans_assign(x, c):
+    """Nearest centroid of every row of x (n x d) among c (k x d) by |c_j|^2 - 2 x.c_j, ties to the lowest j.
+    Returns (ids (n,) int32, squared distances (n,) float32)."""
+    n, k = int(x.shape[0]), int(c.shape[0])
+    if int(c.shape[1]) != int(x.shape[1]):
+        raise SelfrecHipError("kmeans_assign: x and c must have the same number of columns")
+    xp, cp = _km_padded(x, "kmeans_assign"), _km_padded(c, "kmeans_assign")
+    ids = torch.empty(n, dtype=torch.int32, device=x.device)
+    dist = torch.empty(n, dtype=torch.float32, device=x.device)
+    check(_lib.load().srh_kmeans_assign_f32(_p(xp, torch.float32, "x"), n, _p(cp, torch.float32, "c"), k, int(xp.shape[1]),
+                                            _p(ids), _p(dist), _stream()), "srh_kmeans_assign_f32")
+    return ids, dist
+
+
+def kmeans_update(x, ids, k, ws=None):
+    """Per-cluster means and counts of the rows of x (n x d) under ids (n,), each cluster summed in ascending row
+    order (bit-identical from call to call).  Returns (centroids (k x d) float32, counts (k,) int32); an empty cluster
+    has a zero centroid and count 0."""
+    n, d = int(x.shape[0]), int(x.shape[1])
+    ids = ids.to(torch.int32).contiguous()
+    cent = torch.empty((int(k), d), dtype=torch.float32, device=x.device)
+    counts = torch.empty(int(k), dtype=torch.int32, device=x.device)
+    need = int(_lib.load().srh_kmeans_update_ws_bytes(n, int(k)))
+    if ws is None or ws.numel() * ws.element_size() < need:
+        ws = torch.empty(need, dtype=torch.uint8, device=x.device)
+    check(_lib.load().srh_kmeans_update_f32(_p(x, torch.float32, "x"), n, _p(ids, torch.int32, "ids"), int(k), d, _p(cent),
+                                            _p(counts), _p(ws), _stream()), "srh_kmeans_update_f32")
+    return cent, counts
+
+
+KMEANS_MAX_POINTS_PER_CENTROID = 256          # faiss ClusteringParameters.max_points_per_centroid
+KMEANS_SPLIT_EPS = 1.0 / 1024.0               # faiss Clustering.cpp split_clusters: EPS
+
+
+def kmeans_split(centroids, counts):
+    """faiss's empty-cluster handling made deterministic (host, in place): every empty cluster, in ascending id, takes
+    the largest cluster (lowest id on ties) as its donor, copies its centroid with the +-1/1024 symmetric perturbation
+    (even coordinates x(1+eps) on the empty one and x(1-eps) on the donor, odd the other way round) and half its
+    count.  centroids: (k, d) float32 numpy, counts: (k,) int64 numpy.  Returns the number of splits."""
+    eps = np.float32(KMEANS_SPLIT_EPS)
+    up, down = np.float32(1) + eps, np.float32(1) - eps
+    nsplit = 0
+    for ci in np.flatnonzero(counts == 0):
+        if counts[ci] != 0:
+            continue
+        cj = int(np.argmax(counts))
+        centroids[ci] = centroids[cj]
+        centroids[ci, 0::2] *= up
+        centroids[cj, 0::2] *= down
+        centroids[ci, 1::2] *= down
+        centroids[cj, 1::2] *= up
+        counts[ci] = counts[cj] // 2
+        counts[cj] -= counts[ci]
+        nsplit += 1
+    return nsplit
+
+
+def kmeans(x, k, niter=25, seed=1234, stats=None):
+    """k-means of the rows of x (n x d, on the device) under the defaults of faiss.Kmeans(d, k) as NCL.py:37 uses it,
+    with the random choices made deterministic:
+      1. perm = np.random.RandomState(seed).permutation(n); n > 256 k: train on rows perm[:256 k]; initial centroids =
+         rows perm[:k]
+      2. niter times: assign (kmeans_assign), update (kmeans_update), split empty clusters (kmeans_split)
+      3. assign all n rows against the final centroids (kmeans.index.search(x, 1))
+    Returns (centroids (k, d) float32, assignment (n,) int64), both on the device.  ``stats`` (a dict, optional)
+    receives the per-iteration objective (sum of squared distances, before that iteration's update) and the smallest
+    count after each update's splits."""
+    if x.dim() != 2:
+        raise SelfrecHipError("kmeans: x must be 2-D")
+    n, k = int(x.shape[0]), int(k)
+    if k < 1:
+        raise SelfrecHipError("kmeans: k must be >= 1")
+    if k > n:
+        raise SelfrecHipError(f"kmeans: {n} points are not enough to train {k} centroids (need k <= n)")
+    d = int(x.shape[1])
+    x = x.detach().float().contiguous()
+    xp = _km_padded(x, "kmeans")
+    perm = np.random.RandomState(seed).permutation(n)
+    if n > KMEANS_MAX_POINTS_PER_CENTROID * k:
+        xt = xp.index_select(0, torch.from_numpy(perm[:KMEANS_MAX_POINTS_PER_CENTROID * k]).to(xp.device)).contiguous()
+    else:
+        xt = xp
+    cent = xp.index_select(0, torch.from_numpy(perm[:k]).to(xp.device)).contiguous()
+    need = int(_lib.load().srh_kmeans_update_ws_bytes(int(xt.shape[0]), k))
+    ws = torch.empty(need, dtype=torch.uint8, device=x.device)
+    if stats is not None:
+        stats.setdefault("obj", [])
+        stats.setdefault("min_count", [])
+    for _ in range(int(niter)):
+        ids, dist = kmeans_assign(xt, cent)
+        if stats is not None:
+            stats["obj"].append(float(dist.double().sum()))
+        cent, counts = kmeans_update(xt, ids, k, ws)
+        counts_h = counts.cpu().numpy().astype(np.int64)
+        if (counts_h == 0).any():
+            cent_h = cent.cpu().numpy()
+            kmeans_split(cent_h, counts_h)
+            cent = torch.from_numpy(cent_h).to(x.device)
+        if stats is not None:
+            stats["min_count"].append(int(counts_h.min()))
+    ids, _ = kmeans_assign(xp, cent)
+    return cent[:, :d].contiguous(), ids.long()
