@@ -118,6 +118,11 @@ srh_status_t srh_sampler_next_u32(srh_sampler_t* s, uint32_t* out);
 srh_status_t srh_find_k_largest_host(int64_t k, const float* h_candidates, int64_t n, int64_t* h_out_ids,
                                      float* h_out_scores, int64_t* out_count);
 
+/* The same walk for float64 candidates (UserKNN / ItemKNN scores: base/graph_recommender.py:47-51 on predict()'s
+ * float64 row). */
+srh_status_t srh_find_k_largest_host_f64(int64_t k, const double* h_candidates, int64_t n, int64_t* h_out_ids,
+                                         double* h_out_scores, int64_t* out_count);
+
 /* `torch.rand(n)` of the CPU generator (ATen: mt19937, one 32-bit word per float32, value = (word & 0xFFFFFF) * 2^-24),
  * replayed on the host from the generator's own words: what model/graph/BUIR.py:118-121 draws per forward pass for its
  * sparse dropout -- `torch.floor(keep_prob + torch.rand(nnz)).type(torch.bool)` -- at 5 M entries per step on the Yelp2018
@@ -764,6 +769,40 @@ int64_t srh_kmeans_update_ws_bytes(int64_t n, int64_t k);
 srh_status_t srh_kmeans_update_f32(const float* d_x, int64_t n, const int32_t* d_ids, int64_t k,
                                    int32_t d, float* d_out_centroids, int32_t* d_out_counts,
                                    void* d_ws, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * (a-14) UserKNN / ItemKNN -- replace model/graph/UserKNN.py:32-57 / ItemKNN.py:32-56 (train: every row against every
+ * other row in python) and :59-81 (predict), ranked as base/graph_recommender.py:44-58 ranks them.
+ *
+ * srh_knn_neighbours: rows of a binary matrix A (n_rows rows; d_a_* its CSR, d_t_* the transposed CSR with every row's
+ *   entries ASCENDING).  For query row q (d_query_rows[i], or row i when NULL) and every other row v sharing n > 0
+ *   features with it:
+ *       sim = (n / (n + s)) * (n / (norm[q] * norm[v] + 1e-8))     (s = shrinkage, each operation a rounded f64 one)
+ *   d_norm[v] = sqrt((double)|A_v|) (np.sqrt of the degree, computed by the caller).  The best k by (sim desc,
+ *   d_name_rank desc) -- heapq.nlargest(k, [(sim, name), ...]) when d_name_rank[v] is the rank of v's name in
+ *   sorted(names).  Outputs (n_query x k, best first): d_out_ids (-1 padded), d_out_sims (0.0 padded), d_out_len.
+ *   1 <= k <= 128.  Integer LDS counters, no float atomics: the same bits on every call.
+ * srh_knn_score_topk: for each query user (d_users, n_query), the f64 row of UserKNN.predict (mode 0: d_nbr_* are the
+ *   user lists; every training item of every neighbour, in list order) or ItemKNN.predict (mode 1: d_nbr_* are the
+ *   item lists; for each training item i of the user in d_r_indices order, every item of i's list):
+ *       score = S / (S + 1e-8) where touched (S: the sum of the sims added, in that order), 0.0 elsewhere
+ *   with the user's training items at -10e8 when mask_train != 0 (predict() itself does not mask them); then the best
+ *   n_top + 1 by (score desc, id asc).  Outputs (n_query x n_top): the first n_top, and rows in which two NEIGHBOURS
+ *   of the n_top + 1 are equal marked d_out_ids[row][0] = -1 - id (srh_topk_trim_mark_ties' contract: the caller redoes them with srh_find_k_largest_host_f64).
+ *   d_r_indptr / d_r_indices: users x items, each user's items in training-file order.  n_top + 1 <= min(128, n_items).
+ *   d_ws >= srh_knn_score_ws_bytes(ws_rows, n_items): ws_rows f64 score rows; the users pass through them ws_rows at a
+ *   time.  When n_query <= ws_rows, row q of d_ws holds query q's finished score row after the call.
+ * ---------------------------------------------------------------------------------- */
+srh_status_t srh_knn_neighbours(const int32_t* d_a_indptr, const int32_t* d_a_indices, const int32_t* d_t_indptr,
+                                const int32_t* d_t_indices, const double* d_norm, const int32_t* d_name_rank, int64_t n_rows,
+                                const int32_t* d_query_rows, int64_t n_query, int32_t k, int32_t shrinkage,
+                                int32_t* d_out_ids, double* d_out_sims, int32_t* d_out_len, void* stream);
+int64_t srh_knn_score_ws_bytes(int64_t ws_rows, int64_t n_items);
+srh_status_t srh_knn_score_topk(int32_t mode, const int32_t* d_users, int64_t n_query, const int32_t* d_r_indptr,
+                                const int32_t* d_r_indices, int64_t n_items, const int32_t* d_nbr_ids,
+                                const double* d_nbr_sims, const int32_t* d_nbr_len, int32_t k_nbr, int32_t n_top,
+                                int32_t mask_train, void* d_ws, int64_t ws_rows, int32_t* d_out_ids, double* d_out_scores,
+                                void* stream);
 
 /* ------------------------------------------------------------------------------------
  * (f-1) Dataset files -> id arrays -- replaces the python loops of data/loader.py:22-33

@@ -118,6 +118,7 @@ SIGNATURES = {
     "srh_device_count": (_i32, []),
     "srh_topk_trim_mark_ties": (_i32, [_vp, _vp, _i64, _i32, _vp, _vp, _vp]),
     "srh_find_k_largest_host": (_i32, [_i64, _vp, _i64, _vp, _vp, _vp]),
+    "srh_find_k_largest_host_f64": (_i32, [_i64, _vp, _i64, _vp, _vp, _vp]),
     "srh_sampler_create": (_i32, [C.POINTER(_vp), _i64, _i64, _i64, _vp, _vp]),
     "srh_sampler_destroy": (None, [_vp]),
     "srh_sampler_set_state": (_i32, [_vp, _vp, _i32]),
@@ -161,6 +162,10 @@ SIGNATURES = {
     "srh_kmeans_assign_f32": (_i32, [_vp, _i64, _vp, _i64, _i32, _vp, _vp, _vp]),
     "srh_kmeans_update_ws_bytes": (_i64, [_i64, _i64]),
     "srh_kmeans_update_f32": (_i32, [_vp, _i64, _vp, _i64, _i32, _vp, _vp, _vp, _vp]),
+    "srh_knn_neighbours": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "srh_knn_score_ws_bytes": (_i64, [_i64, _i64]),
+    "srh_knn_score_topk": (_i32, [_i32, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _i64, _vp, _vp,
+                                  _vp]),
     "srh_adam_step": (_i32, [_vp, _vp, _vp, _vp, _i64, _i64, _vp, _f32, _f32, _f32, _f32, _vp]),
     "srh_adam_step_reset": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _vp, _f32, _f32, _f32, _f32, _vp, _i32, _vp, _vp, _vp]),
     "srh_score_mask_topk": (_i32, [_vp, _vp, _i64, _vp, _i64, _i32, _vp, _vp, _i32, _vp, _i64, _vp, _vp, _vp]),

@@ -561,16 +561,20 @@ srh_status_t srh_sampler_next_u32(srh_sampler_t* s, uint32_t* out) {
 // for step (CPython Lib/heapq.py: heapify, _siftup, _siftdown, heapreplace), so that the few rows of a ranking whose best
 // scores tie come out as the reference's would without walking 38 k python floats (6 ms per row).
 // ---------------------------------------------------------------------------------------------------------------
+extern "C++" {
 namespace {
+template <typename T>
 struct HeapItem {
-  float score;
+  T score;
   int64_t pos;
 };
-inline bool heap_less(const HeapItem& a, const HeapItem& b) {          // tuple comparison: score, then position
+template <typename T>
+inline bool heap_less(const HeapItem<T>& a, const HeapItem<T>& b) {    // tuple comparison: score, then position
   return a.score < b.score || (a.score == b.score && a.pos < b.pos);
 }
-void heap_siftdown(HeapItem* heap, int64_t startpos, int64_t pos) {
-  const HeapItem item = heap[pos];
+template <typename T>
+void heap_siftdown(HeapItem<T>* heap, int64_t startpos, int64_t pos) {
+  const HeapItem<T> item = heap[pos];
   while (pos > startpos) {
     const int64_t parent = (pos - 1) >> 1;
     if (!heap_less(item, heap[parent])) break;
@@ -579,9 +583,10 @@ void heap_siftdown(HeapItem* heap, int64_t startpos, int64_t pos) {
   }
   heap[pos] = item;
 }
-void heap_siftup(HeapItem* heap, int64_t n, int64_t pos) {
+template <typename T>
+void heap_siftup(HeapItem<T>* heap, int64_t n, int64_t pos) {
   const int64_t startpos = pos;
-  const HeapItem item = heap[pos];
+  const HeapItem<T> item = heap[pos];
   int64_t child = 2 * pos + 1;
   while (child < n) {                                                   // bubble the smaller child up until a leaf ...
     const int64_t right = child + 1;
@@ -593,20 +598,17 @@ void heap_siftup(HeapItem* heap, int64_t n, int64_t pos) {
   heap[pos] = item;                                                     // ... then sift the item down from there
   heap_siftdown(heap, startpos, pos);
 }
-}  // namespace
 
-srh_status_t srh_find_k_largest_host(int64_t k, const float* h_candidates, int64_t n, int64_t* h_out_ids, float* h_out_scores,
-                                     int64_t* out_count) {
-  SRH_REQUIRE(h_candidates && h_out_ids && h_out_scores && out_count, "find_k_largest_host: null argument");
-  SRH_REQUIRE(k >= 1 && n >= 0, "find_k_largest_host: bad K or length");
+template <typename T>
+void find_k_largest(int64_t k, const T* h_candidates, int64_t n, int64_t* h_out_ids, T* h_out_scores, int64_t* out_count) {
   const int64_t m = std::min(k, n);                                     // (candidates[:K] of a shorter list: all of it)
-  std::vector<HeapItem> heap((size_t)m);
+  std::vector<HeapItem<T>> heap((size_t)m);
   for (int64_t i = 0; i < m; ++i) heap[(size_t)i] = {h_candidates[i], i};
   for (int64_t i = m / 2 - 1; i >= 0; --i) heap_siftup(heap.data(), m, i);            // heapq.heapify
-  HeapItem* hp = heap.data();
-  float root = m > 0 ? hp[0].score : 0.f;
+  HeapItem<T>* hp = heap.data();
+  T root = m > 0 ? hp[0].score : T(0);
   for (int64_t i = k; i < n; ++i) {
-    const float c = h_candidates[i];
+    const T c = h_candidates[i];
     if (c > root) {                                                     // heapq.heapreplace
       hp[0] = {c, i};
       heap_siftup(hp, m, 0);
@@ -614,12 +616,29 @@ srh_status_t srh_find_k_largest_host(int64_t k, const float* h_candidates, int64
     }
   }
   // heap.sort(key=score, reverse=True): stable, equal scores keep their order in the heap array
-  std::stable_sort(heap.begin(), heap.end(), [](const HeapItem& a, const HeapItem& b) { return a.score > b.score; });
+  std::stable_sort(heap.begin(), heap.end(), [](const HeapItem<T>& a, const HeapItem<T>& b) { return a.score > b.score; });
   for (int64_t i = 0; i < m; ++i) {
     h_out_ids[i] = heap[(size_t)i].pos;
     h_out_scores[i] = heap[(size_t)i].score;
   }
   *out_count = m;
+}
+}  // namespace
+}  // extern "C++"
+
+srh_status_t srh_find_k_largest_host(int64_t k, const float* h_candidates, int64_t n, int64_t* h_out_ids, float* h_out_scores,
+                                     int64_t* out_count) {
+  SRH_REQUIRE(h_candidates && h_out_ids && h_out_scores && out_count, "find_k_largest_host: null argument");
+  SRH_REQUIRE(k >= 1 && n >= 0, "find_k_largest_host: bad K or length");
+  find_k_largest(k, h_candidates, n, h_out_ids, h_out_scores, out_count);
+  return SRH_OK;
+}
+
+srh_status_t srh_find_k_largest_host_f64(int64_t k, const double* h_candidates, int64_t n, int64_t* h_out_ids,
+                                         double* h_out_scores, int64_t* out_count) {
+  SRH_REQUIRE(h_candidates && h_out_ids && h_out_scores && out_count, "find_k_largest_host_f64: null argument");
+  SRH_REQUIRE(k >= 1 && n >= 0, "find_k_largest_host_f64: bad K or length");
+  find_k_largest(k, h_candidates, n, h_out_ids, h_out_scores, out_count);
   return SRH_OK;
 }
 

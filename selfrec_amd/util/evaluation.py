@@ -51,11 +51,13 @@ class RankedLists(dict):
         if self._names_list is None:
             self._names_list = self.item_names.tolist() if hasattr(self.item_names, "tolist") else list(self.item_names)
         ids = np.ascontiguousarray(self.ids, dtype=np.int32)
-        scores = np.ascontiguousarray(self.scores, dtype=np.float32)
+        # float64 scores (UserKNN / ItemKNN) stay float64: the python rows below; _reclist takes float32
+        wide = np.asarray(self.scores).dtype == np.float64
+        scores = np.ascontiguousarray(self.scores, dtype=np.float64 if wide else np.float32)
         was_on = gc.isenabled()
         gc.disable()
         try:
-            if _reclist is not None:
+            if _reclist is not None and not wide:
                 return _reclist.build(self.users, self._names_list, ids, scores, int(ids.shape[1]))
             # the same rows in python (host-only formatting of results the device already ranked: 2-3 x slower, same objects)
             names = self._names_list
