@@ -805,6 +805,51 @@ srh_status_t srh_knn_score_topk(int32_t mode, const int32_t* d_users, int64_t n_
                                 void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * (a-15) SSL4Rec -- replaces the towers and losses of model/graph/SSL4Rec.py:25-46 (DNN_Encoder.user_tower /
+ * item_tower: Linear(64, 1024) -> ReLU -> Linear(1024, 128) -> Tanh) and util/loss_torch.py:25-32 (batch_softmax_loss).
+ *
+ * srh_tower_fwd_f32: out (n x 128) = tanh(W2 relu(W1 x_r + b1) + b2) for rows x_r = d_table[d_idx[r]] (d_table[r] when
+ *   d_idx is NULL; an id outside [0, n_table) reads a zero row).  Rows r >= mask_row0 take feature dropout: x * m with
+ *   m = keep ? 1 / (1 - drop_p) : 0 (nn.Dropout's scaled mask).  keep[r][c] is d_mask_in[(r - mask_row0) * 64 + c] != 0
+ *   when d_mask_in is given, else it is drawn from the counter RNG of the SpMM epilogue (tests/counter_rng.py): the word
+ *   of column c in float4 c / 4 at counter rng_counter + (r - mask_row0), keep = u01(word) >= drop_p -- a pure function
+ *   of (seed, counter, row, column).  d_mask_out (optional) receives keep as 0 / 1 bytes in the same layout; d_x_out
+ *   (n x 64, optional) the input after gather and dropout, d_hidden (n x 1024, optional) the post-ReLU hidden layer:
+ *   what srh_tower_bwd_f32 reads.  The weights are nn.Linear's: W1 (1024 x 64), W2 (128 x 1024) row-major.
+ * srh_tower_bwd_f32: from the forward's x, hidden and out and the upstream d_gy (n x 128): d_gx (n x 64, the gradient
+ *   w.r.t. the gathered rows before dropout: already multiplied by the mask of rows >= mask_row0 when d_mask is given),
+ *   d_gw1, d_gb1, d_gw2, d_gb2 (written, not added).  Reductions over rows in a fixed order, no float atomics: the same
+ *   bits on every call.  d_ws >= srh_tower_bwd_ws_bytes(n).
+ * srh_rows_segment_sum_f32: d_out[d_seg_row[s]] += sum of rows d_order[d_seg_start[s] .. d_seg_start[s + 1]) of d_x
+ *   (n_rows x d), in that order: the deterministic scatter-add of gathered-row gradients into a table (the segments are
+ *   a stable sort of the row ids; each table row at most once).
+ * srh_batch_softmax_fwd_bwd: u = normalize(U), v = normalize(V) (B x d each), p_b = exp(u_b.v_b / tau) / sum_j
+ *   exp(u_b.v_j / tau);  *d_loss = mean_b -log(p_b + 1e-5) (double), d_gu / d_gv its gradients w.r.t. U and V (written).
+ *   The B x B logits are never materialised.  d = 64 or 128; d_ws >= srh_batch_softmax_ws_bytes(B, d).
+ * ---------------------------------------------------------------------------------- */
+typedef struct srh_tower_weights {
+  const float* d_w1; /* (1024, 64) */
+  const float* d_b1; /* (1024) */
+  const float* d_w2; /* (128, 1024) */
+  const float* d_b2; /* (128) */
+} srh_tower_weights_t;
+srh_status_t srh_tower_fwd_f32(const float* d_table, const int32_t* d_idx, int64_t n, int64_t n_table,
+                               const srh_tower_weights_t* w, int64_t mask_row0, const uint8_t* d_mask_in,
+                               uint64_t rng_seed, uint64_t rng_counter, float drop_p, uint8_t* d_mask_out,
+                               float* d_x_out, float* d_hidden, float* d_out, void* stream);
+int64_t srh_tower_bwd_ws_bytes(int64_t n);
+srh_status_t srh_tower_bwd_f32(const float* d_x, const float* d_hidden, const float* d_y, const float* d_gy, int64_t n,
+                               const srh_tower_weights_t* w, int64_t mask_row0, const uint8_t* d_mask, float drop_p,
+                               float* d_gx, float* d_gw1, float* d_gb1, float* d_gw2, float* d_gb2, void* d_ws,
+                               void* stream);
+srh_status_t srh_rows_segment_sum_f32(const float* d_x, int64_t n_rows, int32_t d, const int32_t* d_order,
+                                      const int32_t* d_seg_start, const int32_t* d_seg_row, int64_t n_seg,
+                                      int64_t n_table, float* d_out, void* stream);
+int64_t srh_batch_softmax_ws_bytes(int64_t B, int32_t d);
+srh_status_t srh_batch_softmax_fwd_bwd(const float* d_u, const float* d_v, int64_t B, int32_t d, float tau,
+                                       double* d_loss, float* d_gu, float* d_gv, void* d_ws, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * (f-1) Dataset files -> id arrays -- replaces the python loops of data/loader.py:22-33
  * (FileIO.load_data_set: one "user item weight" line per interaction, single-space separated)
  * and data/ui_graph.py:29-45 (ids in first-appearance order of the training file; test pairs kept

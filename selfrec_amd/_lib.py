@@ -56,6 +56,11 @@ class L2Block(C.Structure):
     _fields_ = [("d_x", C.c_void_p), ("rows", C.c_int64), ("cols", C.c_int64), ("d_gx", C.c_void_p)]
 
 
+class TowerWeights(C.Structure):
+    """struct srh_tower_weights (include/selfrec_hip.h)."""
+    _fields_ = [("d_w1", C.c_void_p), ("d_b1", C.c_void_p), ("d_w2", C.c_void_p), ("d_b2", C.c_void_p)]
+
+
 SCALAR_WS_BYTES = 64         # SRH_SCALAR_WS_BYTES
 
 
@@ -166,6 +171,14 @@ SIGNATURES = {
     "srh_knn_score_ws_bytes": (_i64, [_i64, _i64]),
     "srh_knn_score_topk": (_i32, [_i32, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _i64, _vp, _vp,
                                   _vp]),
+    "srh_tower_fwd_f32": (_i32, [_vp, _vp, _i64, _i64, C.POINTER(TowerWeights), _i64, _vp, _u64, _u64, _f32, _vp, _vp,
+                                 _vp, _vp, _vp]),
+    "srh_tower_bwd_ws_bytes": (_i64, [_i64]),
+    "srh_tower_bwd_f32": (_i32, [_vp, _vp, _vp, _vp, _i64, C.POINTER(TowerWeights), _i64, _vp, _f32, _vp, _vp, _vp, _vp,
+                                 _vp, _vp, _vp]),
+    "srh_rows_segment_sum_f32": (_i32, [_vp, _i64, _i32, _vp, _vp, _vp, _i64, _i64, _vp, _vp]),
+    "srh_batch_softmax_ws_bytes": (_i64, [_i64, _i32]),
+    "srh_batch_softmax_fwd_bwd": (_i32, [_vp, _vp, _i64, _i32, _f32, _vp, _vp, _vp, _vp, _vp]),
     "srh_adam_step": (_i32, [_vp, _vp, _vp, _vp, _i64, _i64, _vp, _f32, _f32, _f32, _f32, _vp]),
     "srh_adam_step_reset": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _vp, _f32, _f32, _f32, _f32, _vp, _i32, _vp, _vp, _vp]),
     "srh_score_mask_topk": (_i32, [_vp, _vp, _i64, _vp, _i64, _i32, _vp, _vp, _i32, _vp, _i64, _vp, _vp, _vp]),

@@ -161,5 +161,23 @@ __device__ __forceinline__ float wave_sum_f(float v) {
 }
 __device__ __forceinline__ float sgnf(float x) { return (x > 0.f) ? 1.f : ((x < 0.f) ? -1.f : 0.f); }
 
+// Counter-based noise: every element's uniform is a pure function of (seed, counter, element),
+// so there is no generator state in memory and a captured graph replays with fresh noise by
+// bumping one device-side counter.  The mixer is the 2-multiply "lowbias32" integer hash (full
+// avalanche, bias < 0.2 bits): the perturbation only needs decorrelated U[0,1) draws, and
+// profiling showed the SpMM row epilogue -- not memory -- bounding the kernel, where Philox4x32-10
+// costs ~100 VALU ops per float4 against ~35 here.
+__device__ __forceinline__ uint32_t lowbias32(uint32_t x) {
+  x ^= x >> 16; x *= 0x7feb352dU; x ^= x >> 15; x *= 0x846ca68bU; x ^= x >> 16;
+  return x;
+}
+__device__ __forceinline__ uint4 counter_rng4(uint64_t ctr, uint32_t sub, uint32_t seed_lo, uint32_t seed_hi) {
+  const uint32_t key = lowbias32((uint32_t)ctr ^ seed_lo) + lowbias32((uint32_t)(ctr >> 32) ^ seed_hi);
+  const uint32_t base = key + sub * 0x9E3779B1U;
+  return make_uint4(lowbias32(base), lowbias32(base + 0x85EBCA6BU), lowbias32(base + 0xC2B2AE35U),
+                    lowbias32(base + 0x27D4EB2FU));
+}
+__device__ __forceinline__ float u01(uint32_t x) { return (float)(x >> 8) * (1.0f / 16777216.0f); }
+
 }  // namespace srh
 #endif

@@ -24,7 +24,9 @@ __all__ = ["Sampler", "DeviceCSR", "column_class_order", "spmm", "spmm_any", "pa
            "sumsq", "set_infonce_precision", "get_infonce_precision", "infonce_fwd_bwd", "infonce_multi", "bpr_infonce", "infonce_ws", "adam_step", "score_mask_topk", "score_mask_topk_filtered", "gemm_nt", "topk_rows", "topk_hit_flags", "metric_rows",
            "axpby", "batch_fetch", "zero_rows", "cursor_advance", "batch_lists", "batch_pack", "batch_unpack", "batch_scatter",
            "table_nce_ws", "table_nce_fwd_bwd", "kmeans_assign", "kmeans_update", "kmeans",
-           "find_k_largest_host_f64", "knn_neighbours", "knn_score_ws", "knn_score_topk", "SelfrecHipError"]
+           "find_k_largest_host_f64", "knn_neighbours", "knn_score_ws", "knn_score_topk",
+           "tower_fwd", "tower_bwd", "scatter_plan", "rows_segment_sum", "batch_softmax_fwd_bwd", "TowerFn",
+           "BatchSoftmaxFn", "SelfrecHipError"]
 
 
 def _stream() -> int:
@@ -1255,3 +1257,172 @@ def knn_score_topk(mode, users, r_indptr, r_indices, n_items, nbr_ids, nbr_sims,
                                          _p(sc), _stream()),
           "srh_knn_score_topk")
     return ids, sc, ws
+
+
+# ---- SSL4Rec: the MLP towers and batch_softmax_loss (csrc/ssl4rec.hip) ----------------------------------------------------
+TOWER_IN, TOWER_HIDDEN, TOWER_OUT = 64, 1024, 128
+BATCH_SOFTMAX_WIDTHS = (64, 128)
+
+
+def _tower_weights(w1, b1, w2, b2):
+    shapes = ((w1, (TOWER_HIDDEN, TOWER_IN)), (b1, (TOWER_HIDDEN,)), (w2, (TOWER_OUT, TOWER_HIDDEN)), (b2, (TOWER_OUT,)))
+    for t, shape in shapes:
+        if tuple(t.shape) != shape:
+            raise SelfrecHipError(f"tower: weight of shape {tuple(t.shape)}, expected {shape} (Linear(64, 1024) -> ReLU -> "
+                                  f"Linear(1024, 128) -> Tanh)")
+    return _lib.TowerWeights(_p(w1, torch.float32, "w1"), _p(b1, torch.float32, "b1"), _p(w2, torch.float32, "w2"),
+                             _p(b2, torch.float32, "b2"))
+
+
+def tower_fwd(table, idx, w1, b1, w2, b2, *, mask_row0=None, mask=None, drop_p=0.0, rng_seed=0, rng_counter=0,
+              save=True):
+    """DNN_Encoder's tower (SSL4Rec.py:66-77) over rows table[idx] (table itself when idx is None): (y (n x 128),
+    saved) with saved = (x, hidden, keep) for tower_bwd, or None when save is False.
+
+    Rows r >= mask_row0 take nn.Dropout(drop_p): ``mask`` (uint8 (n - mask_row0, 64), 1 = keep) replays given masks;
+    without it keep is drawn in-kernel at counter rng_counter + (r - mask_row0) (include/selfrec_hip.h) and returned in
+    saved[2].  mask_row0 None: no dropout."""
+    if table.dim() != 2 or int(table.shape[1]) != TOWER_IN:
+        raise SelfrecHipError(f"tower: rows of {TOWER_IN} columns expected, got {tuple(table.shape)}")
+    n = int(table.shape[0]) if idx is None else int(idx.numel())
+    if n < 1:
+        raise SelfrecHipError("tower: no rows")
+    dev = table.device
+    row0 = n if mask_row0 is None else int(mask_row0)
+    n_mask = n - row0
+    if mask is not None and tuple(mask.shape) != (n_mask, TOWER_IN):
+        raise SelfrecHipError(f"tower: mask of shape {tuple(mask.shape)}, expected {(n_mask, TOWER_IN)}")
+    ip = None if idx is None else idx.to(torch.int32).contiguous()
+    w = _tower_weights(w1, b1, w2, b2)
+    y = torch.empty((n, TOWER_OUT), dtype=torch.float32, device=dev)
+    x = hidden = keep = None
+    if save:
+        x = torch.empty((n, TOWER_IN), dtype=torch.float32, device=dev)
+        hidden = torch.empty((n, TOWER_HIDDEN), dtype=torch.float32, device=dev)
+        if n_mask > 0:
+            keep = mask.contiguous() if mask is not None else torch.empty((n_mask, TOWER_IN), dtype=torch.uint8, device=dev)
+    mask_in = None if (mask is None or n_mask == 0) else mask.contiguous()
+    mask_out = keep if (save and n_mask > 0 and mask is None) else None
+    check(_lib.load().srh_tower_fwd_f32(_p(table, torch.float32, "table"), _p(ip, torch.int32, "idx"), n,
+                                        int(table.shape[0]), C.byref(w), row0, _p(mask_in, torch.uint8, "mask"),
+                                        int(rng_seed) & 0xFFFFFFFFFFFFFFFF, int(rng_counter) & 0xFFFFFFFFFFFFFFFF,
+                                        float(drop_p if n_mask > 0 else 0.0), _p(mask_out), _p(x), _p(hidden), _p(y),
+                                        _stream()),
+          "srh_tower_fwd_f32")
+    return y, ((x, hidden, keep) if save else None)
+
+
+def tower_bwd(saved, y, gy, w1, b1, w2, b2, *, mask_row0=None, drop_p=0.0, ws=None):
+    """Gradients of tower_fwd: (dX (n x 64, w.r.t. the gathered rows), dW1, db1, dW2, db2), every reduction over rows in
+    a fixed order."""
+    x, hidden, keep = saved
+    n = int(x.shape[0])
+    row0 = n if mask_row0 is None else int(mask_row0)
+    dev = x.device
+    w = _tower_weights(w1, b1, w2, b2)
+    need = int(_lib.load().srh_tower_bwd_ws_bytes(n))
+    if ws is None or ws.numel() * ws.element_size() < need:
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    gx = torch.empty((n, TOWER_IN), dtype=torch.float32, device=dev)
+    gw1, gb1 = torch.empty_like(w1), torch.empty_like(b1)
+    gw2, gb2 = torch.empty_like(w2), torch.empty_like(b2)
+    gy = gy.to(torch.float32).contiguous()
+    check(_lib.load().srh_tower_bwd_f32(_p(x), _p(hidden), _p(y, torch.float32, "y"), _p(gy, torch.float32, "gy"), n,
+                                        C.byref(w), row0, _p(keep, torch.uint8, "mask"),
+                                        float(drop_p if keep is not None else 0.0), _p(gx), _p(gw1), _p(gb1), _p(gw2),
+                                        _p(gb2), _p(ws), _stream()),
+          "srh_tower_bwd_f32")
+    return gx, gw1, gb1, gw2, gb2
+
+
+def scatter_plan(ids, device):
+    """The segments of srh_rows_segment_sum_f32 for gathered-row ids (host array): a stable sort of the rows by id, so
+    each table row sums its rows in ascending row order.  -> (order, seg_start, seg_row) int32 device tensors."""
+    ids = np.ascontiguousarray(np.asarray(ids).reshape(-1), dtype=np.int64)
+    order = np.argsort(ids, kind="stable")
+    s = ids[order]
+    first = np.flatnonzero(np.r_[True, s[1:] != s[:-1]]) if s.size else np.zeros(0, dtype=np.int64)
+    seg_start = np.r_[first, s.size].astype(np.int32)
+    seg_row = s[first].astype(np.int32)
+    to = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(device)  # noqa: E731
+    return to(order), to(seg_start), to(seg_row)
+
+
+def rows_segment_sum(x, plan, out):
+    """out[row] += the rows of x that plan (scatter_plan) names for it, in plan order: a deterministic index_add_."""
+    order, seg_start, seg_row = plan
+    n_rows, d = int(x.shape[0]), int(x.shape[1])
+    if int(order.numel()) != n_rows or int(out.shape[1]) != d:
+        raise SelfrecHipError("rows_segment_sum: the plan and the tables do not match")
+    check(_lib.load().srh_rows_segment_sum_f32(_p(x.contiguous(), torch.float32, "x"), n_rows, d,
+                                               _p(order, torch.int32, "order"), _p(seg_start, torch.int32, "seg_start"),
+                                               _p(seg_row, torch.int32, "seg_row"), int(seg_row.numel()),
+                                               int(out.shape[0]), _p(out, torch.float32, "out"), _stream()),
+          "srh_rows_segment_sum_f32")
+    return out
+
+
+def batch_softmax_fwd_bwd(u, v, tau, ws=None):
+    """batch_softmax_loss (util/loss_torch.py:25-32) and its gradients: (loss (0-dim float64), dL/du, dL/dv).  Rows up to
+    128 columns (narrower ones zero-padded: no result changes)."""
+    if u.dim() != 2 or u.shape != v.shape:
+        raise SelfrecHipError("batch_softmax: u and v must be 2-D of the same shape")
+    B, d = int(u.shape[0]), int(u.shape[1])
+    w = padded_width(d, BATCH_SOFTMAX_WIDTHS)
+    if w is None:
+        raise SelfrecHipError(f"batch_softmax: rows of {d} columns -- the kernel serves up to {BATCH_SOFTMAX_WIDTHS[-1]}")
+    up, vp = pad_cols(u.float(), w), pad_cols(v.float(), w)
+    dev = u.device
+    need = int(_lib.load().srh_batch_softmax_ws_bytes(B, w))
+    if ws is None or ws.numel() * ws.element_size() < need:
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    loss = torch.empty((), dtype=torch.float64, device=dev)
+    gu = torch.empty((B, w), dtype=torch.float32, device=dev)
+    gv = torch.empty((B, w), dtype=torch.float32, device=dev)
+    check(_lib.load().srh_batch_softmax_fwd_bwd(_p(up, torch.float32, "u"), _p(vp, torch.float32, "v"), B, w, float(tau),
+                                                _p(loss), _p(gu), _p(gv), _p(ws), _stream()),
+          "srh_batch_softmax_fwd_bwd")
+    return loss, gu[:, :d], gv[:, :d]
+
+
+class BatchSoftmaxFn(torch.autograd.Function):
+    """batch_softmax_loss as one kernel call: loss and both gradients come out together; backward() scales them."""
+
+    @staticmethod
+    def forward(ctx, u, v, tau):
+        loss, gu, gv = batch_softmax_fwd_bwd(u, v, tau)
+        ctx.save_for_backward(gu, gv)
+        return loss.to(torch.float32)
+
+    @staticmethod
+    def backward(ctx, gout):
+        gu, gv = ctx.saved_tensors
+        return gu * gout, gv * gout, None
+
+
+class TowerFn(torch.autograd.Function):
+    """y = tower(table[idx]) with the gradient of the WHOLE table (zero outside the rows idx names; repeated ids summed in
+    ascending row order by ``plan`` = scatter_plan(idx)) and of the four weight tensors.  ``keep_out`` (optional list)
+    receives the dropout keep mask the forward used."""
+
+    @staticmethod
+    def forward(ctx, table, w1, b1, w2, b2, idx, plan, mask_row0, mask, drop_p, rng_seed, rng_counter, keep_out):
+        y, saved = tower_fwd(table, idx, w1, b1, w2, b2, mask_row0=mask_row0, mask=mask, drop_p=drop_p,
+                             rng_seed=rng_seed, rng_counter=rng_counter)
+        if keep_out is not None:
+            keep_out.append(saved[2])
+        ctx.save_for_backward(table, w1, b1, w2, b2, y)
+        ctx.x, ctx.hidden, ctx.keep, ctx.idx, ctx.plan, ctx.mask_row0, ctx.drop_p = (*saved, idx, plan, mask_row0, drop_p)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        table, w1, b1, w2, b2, y = ctx.saved_tensors
+        gx, gw1, gb1, gw2, gb2 = tower_bwd((ctx.x, ctx.hidden, ctx.keep), y, gy, w1, b1, w2, b2, mask_row0=ctx.mask_row0,
+                                           drop_p=ctx.drop_p)
+        if ctx.idx is None:
+            gt = gx
+        else:
+            plan = ctx.plan if ctx.plan is not None else scatter_plan(ctx.idx.cpu().numpy(), table.device)
+            gt = rows_segment_sum(gx, plan, torch.zeros_like(table))
+        return gt, gw1, gb1, gw2, gb2, None, None, None, None, None, None, None, None

@@ -1,5 +1,5 @@
 """Differentiable losses with the signatures of reference util/loss_torch.py
-(``bpr_loss`` :6-10, ``l2_reg_loss`` :18-22, ``InfoNCE`` :35-50), computed by fused HIP
+(``bpr_loss`` :6-10, ``l2_reg_loss`` :18-22, ``batch_softmax_loss`` :25-32, ``InfoNCE`` :35-50), computed by fused HIP
 forward+backward kernels.
 
 What runs where:
@@ -123,6 +123,27 @@ def l2_reg_loss(reg, *args):
         else:
             emb_loss = emb_loss + torch.norm(emb, p=2) / emb.shape[0]          # loss_torch.py:18-22
     return emb_loss * reg
+
+
+def _batch_softmax_expression(user_emb, item_emb, temperature):
+    """loss_torch.py:25-32"""
+    user_emb, item_emb = F.normalize(user_emb, dim=1), F.normalize(item_emb, dim=1)
+    pos_score = (user_emb * item_emb).sum(dim=-1)
+    pos_score = torch.exp(pos_score / temperature)
+    ttl_score = torch.matmul(user_emb, item_emb.transpose(0, 1))
+    ttl_score = torch.exp(ttl_score / temperature).sum(dim=1)
+    loss = -torch.log(pos_score / ttl_score + 10e-6)
+    return torch.mean(loss)
+
+
+def batch_softmax_loss(user_emb, item_emb, temperature):
+    """mean_b -log(p_bb + 1e-5) of the in-batch softmax (SSL4Rec.py:33): one HIP call (ops.BatchSoftmaxFn) produces the
+    loss and both gradients without the B x B logits; rows up to 128 columns."""
+    if not _on_hip_path(user_emb, item_emb):
+        return _batch_softmax_expression(user_emb, item_emb, temperature)
+    if user_emb.shape != item_emb.shape:
+        raise ops.SelfrecHipError("batch_softmax_loss: the two sides must have the same shape")
+    return ops.BatchSoftmaxFn.apply(user_emb, item_emb, float(temperature))
 
 
 class _InfoNceFn(torch.autograd.Function):
