@@ -36,6 +36,9 @@ inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s);
 
 constexpr int kWave = 64;  // gfx950 wavefront
 
+// workspace carving: every array starts on a 256-byte boundary
+inline int64_t align256(int64_t b) { return (b + 255) & ~int64_t(255); }
+
 // lanes per embedding row when each lane owns one float4 of it
 inline bool dim_supported(int d) { return d == 32 || d == 64 || d == 128 || d == 256; }
 

@@ -1,0 +1,422 @@
+// Unit-row InfoNCE by two MFMA passes, with no logits matrix and no float atomics: NCL's table loss and SSL4Rec's
+// batch_softmax_loss.  DESIGN.md 4.6 and 4.8.
+//
+// Per problem: queries Q (B x D), keys T (N x D) and the positive key of each query, pos(b) = idx[b], or b itself when
+// idx is null (then N = B).  q = normalize(Q_b), t = normalize(T_j) (F.normalize: x / max(|x|, 1e-12)),
+// e_bj = exp(q_b.t_j / tau), P_bj = e_bj / sum_j e_bj.
+//   table InfoNCE (srh_table_nce_fwd_bwd, NCL.py:57-83 ssl_layer_loss; one or two problems, each with a loss scale s)
+//     loss = s sum_b [ -q_b.t_idx[b] / tau + log sum_j e_bj ]          dL/ds_bj = s (P_bj - [j == idx_b]) / tau
+//   batch softmax (srh_batch_softmax_fwd_bwd, util/loss_torch.py:25-32; one problem, T = V, the identity as positives)
+//     loss = mean_b -log(p_b + 1e-5), p_b = P_bb                      dL/ds_bj = w_b (P_bj - [j == b]) / (B tau)
+//     with w_b = p_b / (p_b + 1e-5): InfoNCE's row gradient scaled by w_b.
+// The B x N logits are never materialised.  The rows are unit vectors, so every logit is <= 1/tau and the exponentials
+// are taken as exp((s - 1) / tau): no running max.
+//   prep    normalise Q and T into the workspace (rows and their norms)
+//   pass 1  query tiles x key chunks: per query and chunk, sum_j e_bj and sum_j e_bj t_j (e = exp((s - 1)/tau))
+//   finish  per query: the chunk partials in chunk order -> row sum, loss term, dL/dQ (normalisation backward fused),
+//           and the query's weights for pass 2: cw_b (1 / rowsum; w_b / rowsum) and cd_b (1; w_b)
+//   pass 2  key tiles x all queries: dT_j = g sum_b (e_bj cw_b - [pos(b) == j] cd_b) q_b with the problem's gradient
+//           scale g (s / tau; 1 / (B tau)), normalisation backward fused; each key tile owns its rows of dT
+//   sum     the per-query loss terms in a fixed order
+// Only the finish's loss term and weights, the rounding of pass 2's positive term and the scaling of the sum depend on
+// the loss (the SOFTMAX template flag); everything else is data.  All four products run on v_mfma_f32_16x16x4_f32.  Every
+// output element is produced by one lane in a fixed order, so a call returns the same bits every time.
+//
+// Both passes are one kernel: a workgroup holds 64 "R" rows (16 per wave) in registers and streams "C" rows through LDS.
+//   S^T[c][r] = Cn_c . Rn_r                       (MFMA 1: A = C tile from LDS, B = R rows from registers)
+//   W[c][r]   = weight(S^T[c][r])                 (on the accumulator, in place)
+//   O^T[:, r] += sum_c Cn_c W[c][r]               (MFMA 2: the accumulator of MFMA 1 is its B operand, no lane movement;
+//                                                  the c order inside a k-step is 4*(lane>>4) + reg, matched by A)
+// pass 1: R = queries, C = keys,    W = e                               -> O = sum_j e_bj t_j, and the row sums of W
+// pass 2: R = keys,    C = queries, W = e cw_c - [pos(c) == key] cd_c   -> O = dL/dt / g
+#include <algorithm>
+#include <cmath>
+
+#include "common.h"
+
+namespace {
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+constexpr int kCtWaves = 4;                 // waves per workgroup; each owns 16 R rows
+constexpr int kCtRows = 16 * kCtWaves;      // R rows per workgroup
+constexpr int kCtCTile = 64;                // C rows staged in LDS per iteration
+constexpr int kCtMaxProblems = 2;
+constexpr int kCtPass1Target = 512;         // pass-1 workgroups aimed for per problem (query tiles x key chunks)
+constexpr float kNormEps = 1e-12f;
+constexpr double kBsEps = 1e-5;             // loss_torch.py:31 (10e-6)
+
+struct CtProblem {
+  const float* q;
+  const float* t;
+  const int32_t* idx;  // null: the positive key of query b is row b
+  int64_t B, N;
+  float scale;         // table loss: the loss scale
+  float gscale;        // dL/dt_j = gscale * O_j (then the normalisation backward)
+  double* loss;
+  float* gq;
+  float* gt;
+  // workspace
+  float* qn;        // B x D  normalised queries
+  float* qnorm;     // B      |Q_b|
+  float* tn;        // N x D  normalised keys
+  float* tnorm;     // N      |T_j|
+  float* part_o;    // chunks x B x D  sum_j e_bj t_j per key chunk
+  double* part_rs;  // chunks x B      sum_j e_bj per key chunk
+  float* cw;        // B      pass-2 weight of query b
+  float* cd;        // B      pass-2 weight of query b's positive term
+  double* row_loss; // B
+  int64_t chunks, chunk_len;
+};
+
+struct CtArgs {
+  CtProblem p[kCtMaxProblems];
+  float inv_tau;
+};
+
+// pass-1 key chunks of a problem: a pure function of (B, N), so the workspace query and the launch agree and every
+// call sums in the same order
+inline int64_t ct_chunks(int64_t B, int64_t N) {
+  const int64_t rtiles = (B + kCtRows - 1) / kCtRows;
+  const int64_t ctiles = (N + kCtCTile - 1) / kCtCTile;
+  int64_t c = (kCtPass1Target + rtiles - 1) / rtiles;
+  if (c > ctiles) c = ctiles;
+  return c < 1 ? 1 : c;
+}
+inline int64_t ct_chunk_len(int64_t B, int64_t N) {
+  const int64_t c = ct_chunks(B, N);
+  const int64_t per = (N + c - 1) / c;
+  return (per + kCtCTile - 1) / kCtCTile * kCtCTile;
+}
+
+using srh::align256;
+
+inline int64_t ct_ws_bytes(int64_t B, int64_t N, int D) {
+  const int64_t c = ct_chunks(B, N);
+  return align256(4 * B * D) + align256(4 * B) + align256(4 * N * D) + align256(4 * N) + align256(4 * c * B * D) +
+         align256(8 * c * B) + 2 * align256(4 * B) + align256(8 * B);
+}
+
+void ct_carve(CtProblem& p, char* ws, int D) {
+  char* cur = ws;
+  auto take = [&](int64_t bytes) { char* r = cur; cur += align256(bytes); return r; };
+  p.chunks = ct_chunks(p.B, p.N);
+  p.chunk_len = ct_chunk_len(p.B, p.N);
+  p.qn = (float*)take(4 * p.B * D);
+  p.qnorm = (float*)take(4 * p.B);
+  p.tn = (float*)take(4 * p.N * D);
+  p.tnorm = (float*)take(4 * p.N);
+  p.part_o = (float*)take(4 * p.chunks * p.B * D);
+  p.part_rs = (double*)take(8 * p.chunks * p.B);
+  p.cw = (float*)take(4 * p.B);
+  p.cd = (float*)take(4 * p.B);
+  p.row_loss = (double*)take(8 * p.B);
+}
+
+// d(normalize(x))/dx applied to g: (g - y (y.g)) / |x| where |x| >= eps, g / eps below it (F.normalize's clamp_min)
+__device__ __forceinline__ float norm_bwd_scale(float nrm) { return 1.f / fmaxf(nrm, kNormEps); }
+
+// pass 2's weight of a query's positive term, rounded as each loss has always rounded it: the table loss in one fused
+// multiply-add (e cw - 1), batch softmax after the product (e cw rounded, then - w_b)
+template <bool SOFTMAX>
+__device__ __forceinline__ float pos_weight(float e, float cw, float cd) {
+  if (SOFTMAX) {
+#pragma clang fp contract(off)
+    return e * cw - cd;
+  }
+  return fmaf(e, cw, -cd);
+}
+
+// ---- prep: normalise rows (LPR = D/4 lanes per row, one float4 each) ------------------------------------------------
+template <int D>
+__global__ __launch_bounds__(256) void ct_prep(CtArgs a) {
+  constexpr int LPR = D / 4, RPB = 256 / LPR;
+  const CtProblem& P = a.p[blockIdx.y >> 1];
+  const bool keys = blockIdx.y & 1;
+  const int64_t rows = keys ? P.N : P.B;
+  const float* src = keys ? P.t : P.q;
+  float* dst = keys ? P.tn : P.qn;
+  float* nrm_out = keys ? P.tnorm : P.qnorm;
+  const int64_t row = (int64_t)blockIdx.x * RPB + threadIdx.x / LPR;
+  const int lane = threadIdx.x % LPR;
+  const bool ok = row < rows;
+  const float4 v = ok ? reinterpret_cast<const float4*>(src + row * D)[lane] : srh::f4_zero();
+  const float ss = srh::group_sum<LPR>(srh::f4_dot(v, v));
+  const float nrm = sqrtf(ss);
+  const float den = fmaxf(nrm, kNormEps);
+  if (ok) {
+    reinterpret_cast<float4*>(dst + row * D)[lane] = make_float4(v.x / den, v.y / den, v.z / den, v.w / den);
+    if (lane == 0) nrm_out[row] = nrm;
+  }
+}
+
+// ---- the two passes (SOFTMAX: pass 2's positive-term rounding only) -------------------------------------------------
+template <int D, bool PASS2, bool SOFTMAX>
+__global__ __launch_bounds__(256) void ct_pass(CtArgs a) {
+  constexpr int LDS_STRIDE = D + 4;  // rows 4 floats apart in bank space: both LDS read patterns are conflict-free
+  __shared__ float cs[kCtCTile * LDS_STRIDE];
+  __shared__ float cw[kCtCTile];
+  __shared__ float cd[kCtCTile];
+  __shared__ int32_t cid[kCtCTile];
+  const CtProblem& P = a.p[blockIdx.y];
+  const int64_t nR = PASS2 ? P.N : P.B;
+  const float* Rn = PASS2 ? P.tn : P.qn;
+  const float* Cn = PASS2 ? P.qn : P.tn;
+  const int64_t rtiles = (nR + kCtRows - 1) / kCtRows;
+  const int64_t rtile = PASS2 ? (int64_t)blockIdx.x : (int64_t)blockIdx.x / P.chunks;
+  const int64_t chunk = PASS2 ? 0 : (int64_t)blockIdx.x % P.chunks;
+  if (rtile >= rtiles) return;
+  int64_t cbeg = 0, cend = P.B;
+  if (!PASS2) {
+    cbeg = chunk * P.chunk_len;
+    cend = cbeg + P.chunk_len < P.N ? cbeg + P.chunk_len : P.N;
+  }
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, g = lane >> 4, j16 = lane & 15;
+  const int64_t r = rtile * kCtRows + wave * 16 + j16;
+  const bool rok = r < nR;
+  const float inv_tau = a.inv_tau;
+
+  float rf[D / 4];  // B operand of MFMA 1: Rn[r][4s + g]
+#pragma unroll
+  for (int s = 0; s < D / 4; ++s) rf[s] = rok ? Rn[r * D + 4 * s + g] : 0.f;
+  f32x4 o[D / 16];
+#pragma unroll
+  for (int b = 0; b < D / 16; ++b) o[b] = f32x4{0.f, 0.f, 0.f, 0.f};
+  double rs = 0.0;
+
+  for (int64_t c0 = cbeg; c0 < cend; c0 += kCtCTile) {
+    __syncthreads();
+    for (int e = threadIdx.x; e < kCtCTile * (D / 4); e += 256) {
+      const int i = e / (D / 4), v = e % (D / 4);
+      const int64_t c = c0 + i;
+      const float4 x = c < cend ? reinterpret_cast<const float4*>(Cn + c * D)[v] : srh::f4_zero();
+      *reinterpret_cast<float4*>(&cs[i * LDS_STRIDE + 4 * v]) = x;
+    }
+    if (threadIdx.x < kCtCTile) {
+      const int64_t c = c0 + threadIdx.x;
+      const bool cok = c < cend;
+      if (PASS2) {
+        cw[threadIdx.x] = cok ? P.cw[c] : 0.f;
+        cd[threadIdx.x] = cok ? P.cd[c] : 0.f;
+        cid[threadIdx.x] = !cok ? -1 : P.idx ? P.idx[c] : (int32_t)c;
+      } else {
+        cw[threadIdx.x] = cok ? 1.f : 0.f;
+      }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int sub = 0; sub < kCtCTile / 16; ++sub) {
+      f32x4 s = {0.f, 0.f, 0.f, 0.f};
+      const float* arow = &cs[(sub * 16 + j16) * LDS_STRIDE + g];
+#pragma unroll
+      for (int k = 0; k < D / 4; ++k) s = __builtin_amdgcn_mfma_f32_16x16x4f32(arow[4 * k], rf[k], s, 0, 0, 0);
+      // s[reg] = S^T[c = sub*16 + 4g + reg][r]
+#pragma unroll
+      for (int reg = 0; reg < 4; ++reg) {
+        const int ci = sub * 16 + 4 * g + reg;
+        const float e = expf((s[reg] - 1.f) * inv_tau);
+        float w = e * cw[ci];
+        if (PASS2) {
+          // (computed for every column: a select, not a branch, keeps the LDS reads of a k-step in one 16-byte read each)
+          const float wpos = pos_weight<SOFTMAX>(e, cw[ci], cd[ci]);
+          if ((int64_t)cid[ci] == r) w = wpos;
+        } else {
+          rs += (double)w;
+        }
+        s[reg] = w;
+      }
+#pragma unroll
+      for (int b = 0; b < D / 16; ++b) {
+#pragma unroll
+        for (int reg = 0; reg < 4; ++reg)
+          o[b] = __builtin_amdgcn_mfma_f32_16x16x4f32(cs[(sub * 16 + 4 * g + reg) * LDS_STRIDE + 16 * b + j16], s[reg], o[b],
+                                                      0, 0, 0);
+      }
+    }
+  }
+  // o[b][reg] = O[r][16b + 4g + reg]
+  if (!PASS2) {
+    rs += __shfl_xor(rs, 16);
+    rs += __shfl_xor(rs, 32);
+    if (!rok) return;
+    const int64_t row = chunk * P.B + r;
+    if (g == 0) P.part_rs[row] = rs;
+#pragma unroll
+    for (int b = 0; b < D / 16; ++b)
+      reinterpret_cast<float4*>(P.part_o + row * D + 16 * b + 4 * g)[0] = make_float4(o[b][0], o[b][1], o[b][2], o[b][3]);
+  } else {
+    // dL/dt_j = gscale * O_j; then the normalisation backward of row j
+    const float k = P.gscale;
+    float4 tv[D / 16];
+    float dot = 0.f;
+#pragma unroll
+    for (int b = 0; b < D / 16; ++b) {
+      tv[b] = rok ? reinterpret_cast<const float4*>(P.tn + r * D + 16 * b + 4 * g)[0] : srh::f4_zero();
+      o[b] *= k;
+      dot = fmaf(tv[b].x, o[b][0], fmaf(tv[b].y, o[b][1], fmaf(tv[b].z, o[b][2], fmaf(tv[b].w, o[b][3], dot))));
+    }
+    dot += __shfl_xor(dot, 16);
+    dot += __shfl_xor(dot, 32);
+    if (!rok) return;
+    const float nrm = P.tnorm[r];
+    const float inv = norm_bwd_scale(nrm);
+    const bool clamped = !(nrm > kNormEps);
+#pragma unroll
+    for (int b = 0; b < D / 16; ++b) {
+      float4 out;
+      if (clamped) {
+        out = make_float4(o[b][0] * inv, o[b][1] * inv, o[b][2] * inv, o[b][3] * inv);
+      } else {
+        out = make_float4((o[b][0] - tv[b].x * dot) * inv, (o[b][1] - tv[b].y * dot) * inv,
+                          (o[b][2] - tv[b].z * dot) * inv, (o[b][3] - tv[b].w * dot) * inv);
+      }
+      reinterpret_cast<float4*>(P.gt + r * D + 16 * b + 4 * g)[0] = out;
+    }
+  }
+}
+
+// ---- per-query finish: chunk partials in chunk order -> row sum, loss term, pass-2 weights, dL/dQ -------------------
+template <int D, bool SOFTMAX>
+__global__ __launch_bounds__(256) void ct_finish(CtArgs a) {
+  constexpr int LPR = D / 4, RPB = 256 / LPR;
+  const CtProblem& P = a.p[blockIdx.y];
+  const int64_t b = (int64_t)blockIdx.x * RPB + threadIdx.x / LPR;
+  const int lane = threadIdx.x % LPR;
+  if (b >= P.B) return;  // (whole row groups leave together: group_sum stays within live lanes)
+  double rs = 0.0;
+  float4 o = srh::f4_zero();
+  for (int64_t c = 0; c < P.chunks; ++c) {
+    rs += P.part_rs[c * P.B + b];
+    o = srh::f4_add(o, reinterpret_cast<const float4*>(P.part_o + (c * P.B + b) * D)[lane]);
+  }
+  const int64_t j = P.idx ? (int64_t)P.idx[b] : b;
+  const bool jok = j >= 0 && j < P.N;  // (an index outside the table reads nothing and makes the loss NaN)
+  const float4 q = reinterpret_cast<const float4*>(P.qn + b * D)[lane];
+  const float4 t = jok ? reinterpret_cast<const float4*>(P.tn + j * D)[lane] : srh::f4_zero();
+  const float spos = srh::group_sum<LPR>(srh::f4_dot(q, t));
+  const float inv_rs = (float)(1.0 / rs);
+  const float inv_tau = a.inv_tau;
+  // dL/dq_b = k (O_b / rowsum - t_pos(b))
+  float k = P.gscale;
+  if (SOFTMAX) {
+    const double p = exp(((double)spos - 1.0) * (double)inv_tau) / rs;
+    const double w = p / (p + kBsEps);
+    if (lane == 0) {
+      P.row_loss[b] = -log(p + kBsEps);
+      P.cw[b] = (float)(w / rs);
+      P.cd[b] = (float)w;
+    }
+    k = (float)w * inv_tau / (float)P.B;
+  } else if (lane == 0) {
+    P.row_loss[b] = jok ? (double)inv_tau * (1.0 - (double)spos) + log(rs) : (double)NAN;
+    P.cw[b] = inv_rs;
+    P.cd[b] = 1.f;
+  }
+  float4 gq = make_float4(k * (o.x * inv_rs - t.x), k * (o.y * inv_rs - t.y), k * (o.z * inv_rs - t.z),
+                          k * (o.w * inv_rs - t.w));
+  const float dot = srh::group_sum<LPR>(srh::f4_dot(q, gq));
+  const float nrm = P.qnorm[b];
+  const float inv = norm_bwd_scale(nrm);
+  if (nrm > kNormEps) gq = make_float4(gq.x - q.x * dot, gq.y - q.y * dot, gq.z - q.z * dot, gq.w - q.w * dot);
+  reinterpret_cast<float4*>(P.gq + b * D)[lane] = srh::f4_scale(gq, inv);
+}
+
+// ---- the loss: per-query terms summed in a fixed order, one workgroup per problem; scale s, or the mean ------------
+template <bool SOFTMAX>
+__global__ __launch_bounds__(256) void ct_loss(CtArgs a) {
+  __shared__ double part[256];
+  const CtProblem& P = a.p[blockIdx.x];
+  double s = 0.0;
+  for (int64_t b = threadIdx.x; b < P.B; b += 256) s += P.row_loss[b];
+  part[threadIdx.x] = s;
+  __syncthreads();
+  for (int w = 128; w > 0; w >>= 1) {
+    if ((int)threadIdx.x < w) part[threadIdx.x] += part[threadIdx.x + w];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) P.loss[0] = SOFTMAX ? part[0] / (double)P.B : (double)P.scale * part[0];
+}
+
+template <int D, bool SOFTMAX>
+srh_status_t launch_ct(CtArgs& a, int np, hipStream_t st) {
+  int64_t max_prep = 0, max_p1 = 0, max_fin = 0, max_p2 = 0;
+  constexpr int RPB = 256 / (D / 4);
+  for (int k = 0; k < np; ++k) {
+    const CtProblem& p = a.p[k];
+    const int64_t big = p.N > p.B ? p.N : p.B;
+    max_prep = std::max(max_prep, (big + RPB - 1) / RPB);
+    max_p1 = std::max(max_p1, (p.B + kCtRows - 1) / kCtRows * p.chunks);
+    max_fin = std::max(max_fin, (p.B + RPB - 1) / RPB);
+    max_p2 = std::max(max_p2, (p.N + kCtRows - 1) / kCtRows);
+  }
+  ct_prep<D><<<dim3((unsigned)max_prep, 2 * np), 256, 0, st>>>(a);
+  SRH_LAUNCH_CHECK();
+  ct_pass<D, false, false><<<dim3((unsigned)max_p1, np), 256, 0, st>>>(a);
+  SRH_LAUNCH_CHECK();
+  ct_finish<D, SOFTMAX><<<dim3((unsigned)max_fin, np), 256, 0, st>>>(a);
+  SRH_LAUNCH_CHECK();
+  ct_pass<D, true, SOFTMAX><<<dim3((unsigned)max_p2, np), 256, 0, st>>>(a);
+  SRH_LAUNCH_CHECK();
+  ct_loss<SOFTMAX><<<np, 256, 0, st>>>(a);
+  SRH_LAUNCH_CHECK();
+  return SRH_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t srh_table_nce_ws_bytes(int64_t B, int64_t N, int32_t d) {
+  if (B <= 0 || N <= 0 || (d != 64 && d != 128)) return 0;
+  return ct_ws_bytes(B, N, d);
+}
+
+srh_status_t srh_table_nce_fwd_bwd(const srh_table_nce_problem_t* problems, int32_t n_problems, int32_t d, float tau,
+                                   void* d_ws, void* stream) {
+  SRH_REQUIRE(problems && d_ws, "table_nce_fwd_bwd: null argument");
+  SRH_REQUIRE(n_problems >= 1 && n_problems <= kCtMaxProblems, "table_nce_fwd_bwd: 1..%d problems per call",
+              kCtMaxProblems);
+  SRH_REQUIRE(d == 64 || d == 128, "table_nce_fwd_bwd: d=%d unsupported (64 or 128; narrower rows are zero-padded)", d);
+  SRH_REQUIRE(tau > 0.f && std::isfinite(tau), "table_nce_fwd_bwd: temperature must be positive");
+  CtArgs a{};
+  a.inv_tau = 1.f / tau;
+  char* ws = static_cast<char*>(d_ws);
+  for (int k = 0; k < n_problems; ++k) {
+    const srh_table_nce_problem_t& s = problems[k];
+    SRH_REQUIRE(s.d_q && s.d_t && s.d_idx && s.d_loss && s.d_gq && s.d_gt, "table_nce_fwd_bwd: null tensor in problem %d", k);
+    SRH_REQUIRE(s.B > 0 && s.B < (int64_t(1) << 31) && s.N > 0 && s.N < (int64_t(1) << 31),
+                "table_nce_fwd_bwd: bad B / N in problem %d", k);
+    CtProblem& p = a.p[k];
+    p.q = s.d_q; p.t = s.d_t; p.idx = s.d_idx; p.B = s.B; p.N = s.N; p.scale = s.loss_scale;
+    p.gscale = s.loss_scale * a.inv_tau;
+    p.loss = s.d_loss; p.gq = s.d_gq; p.gt = s.d_gt;
+    ct_carve(p, ws, d);
+    ws += ct_ws_bytes(s.B, s.N, d);
+  }
+  hipStream_t st = srh::as_stream(stream);
+  return d == 64 ? launch_ct<64, false>(a, n_problems, st) : launch_ct<128, false>(a, n_problems, st);
+}
+
+int64_t srh_batch_softmax_ws_bytes(int64_t B, int32_t d) {
+  if (B <= 0 || (d != 64 && d != 128)) return 0;
+  return ct_ws_bytes(B, B, d);
+}
+
+srh_status_t srh_batch_softmax_fwd_bwd(const float* d_u, const float* d_v, int64_t B, int32_t d, float tau,
+                                       double* d_loss, float* d_gu, float* d_gv, void* d_ws, void* stream) {
+  SRH_REQUIRE(d_u && d_v && d_loss && d_gu && d_gv && d_ws, "batch_softmax: null argument");
+  SRH_REQUIRE(B > 0 && B < (int64_t(1) << 31), "batch_softmax: bad B");
+  SRH_REQUIRE(d == 64 || d == 128, "batch_softmax: d=%d unsupported (64 or 128; narrower rows are zero-padded)", d);
+  SRH_REQUIRE(tau > 0.f && std::isfinite(tau), "batch_softmax: temperature must be positive");
+  CtArgs a{};
+  a.inv_tau = 1.f / tau;
+  CtProblem& p = a.p[0];
+  p.q = d_u; p.t = d_v; p.idx = nullptr; p.B = B; p.N = B;
+  p.gscale = a.inv_tau / (float)B;
+  p.loss = d_loss; p.gq = d_gu; p.gt = d_gv;
+  ct_carve(p, static_cast<char*>(d_ws), d);
+  hipStream_t st = srh::as_stream(stream);
+  return d == 64 ? launch_ct<64, true>(a, 1, st) : launch_ct<128, true>(a, 1, st);
+}
+
+}  // extern "C"

@@ -1,4 +1,4 @@
-// SSL4Rec (reference model/graph/SSL4Rec.py): the two MLP towers and batch_softmax_loss.  DESIGN.md 4.8.
+// SSL4Rec (reference model/graph/SSL4Rec.py): the two MLP towers.  DESIGN.md 4.8.
 //
 // Tower (DNN_Encoder.user_tower / item_tower):  Y = tanh(W2 relu(W1 X + b1) + b2),  X (n x 64), W1 (1024 x 64),
 // W2 (128 x 1024), the nn.Linear layouts.
@@ -17,12 +17,8 @@
 //   srh_rows_segment_sum_f32  the deterministic scatter of dX into the embedding-table gradient: rows grouped by the
 //                       host's stable sort of the ids, each table row sums its rows in that order.
 //
-// batch_softmax_loss (util/loss_torch.py:25-32):  u = normalize(U), v = normalize(V), p_b = e_bb / sum_j e_bj with
-// e = exp(u.v / tau);  loss = mean_b -log(p_b + 1e-5).  With w_b = p_b / (p_b + 1e-5) the gradient is InfoNCE's row
-// gradient scaled by w_b:  dL/ds_bj = w_b (P_bj - [b == j]) / (B tau).  The B x B logits are never materialised: the
-// two-pass structure of the table InfoNCE kernel (ncl.hip), with w_b carried into the column pass.
+// batch_softmax_loss (srh_batch_softmax_fwd_bwd) is the shared two-pass kernel of contrastive.hip.
 #include <algorithm>
-#include <cmath>
 
 #include "common.h"
 
@@ -36,10 +32,7 @@ constexpr int kIn = 64, kHid = 1024, kOut = 128;
 constexpr int kHc = 64;                 // hidden units per chunk of the forward walk
 constexpr int kLds = kHc + 4;           // LDS row stride (floats) of the staged chunk
 constexpr int kRowChunk = 256;          // rows per partial of the weight-gradient reductions
-constexpr double kBsEps = 1e-5;         // loss_torch.py:31 (10e-6)
-constexpr float kNormEps = 1e-12f;
 
-inline int64_t align256(int64_t b) { return (b + 255) & ~int64_t(255); }
 __host__ __device__ inline int64_t row_chunks(int64_t n) { return (n + kRowChunk - 1) / kRowChunk; }
 
 struct FwdArgs {
@@ -297,257 +290,6 @@ BwdWs bwd_carve(char* ws, int64_t n) {
   return w;
 }
 
-// ---- batch softmax ---------------------------------------------------------------------------------------------------
-constexpr int kBsRows = 64;           // R rows per workgroup (16 per wave)
-constexpr int kBsCTile = 64;          // C rows staged in LDS per iteration
-constexpr int kBsPass1Target = 512;   // pass-1 workgroups aimed for (row tiles x column chunks)
-
-struct BsArgs {
-  const float *u, *v;
-  int64_t B;
-  float inv_tau;
-  double* loss;
-  float *gu, *gv;
-  float *un, *unorm, *vn, *vnorm;
-  float* part_o;    // chunks x B x D
-  double* part_rs;  // chunks x B
-  float* cw;        // B  w_b / rowsum_b
-  float* wv;        // B  w_b
-  double* row_loss; // B
-  int64_t chunks, chunk_len;
-};
-
-inline int64_t bs_chunks(int64_t B) {
-  const int64_t rtiles = (B + kBsRows - 1) / kBsRows;
-  const int64_t ctiles = (B + kBsCTile - 1) / kBsCTile;
-  int64_t c = (kBsPass1Target + rtiles - 1) / rtiles;
-  if (c > ctiles) c = ctiles;
-  return c < 1 ? 1 : c;
-}
-inline int64_t bs_chunk_len(int64_t B) {
-  const int64_t c = bs_chunks(B);
-  const int64_t per = (B + c - 1) / c;
-  return (per + kBsCTile - 1) / kBsCTile * kBsCTile;
-}
-inline int64_t bs_ws_bytes(int64_t B, int D) {
-  const int64_t c = bs_chunks(B);
-  return 2 * align256(4 * B * D) + 2 * align256(4 * B) + align256(4 * c * B * D) + align256(8 * c * B) +
-         2 * align256(4 * B) + align256(8 * B);
-}
-void bs_carve(BsArgs& a, char* ws, int D) {
-  char* cur = ws;
-  auto take = [&](int64_t bytes) { char* r = cur; cur += align256(bytes); return r; };
-  a.chunks = bs_chunks(a.B);
-  a.chunk_len = bs_chunk_len(a.B);
-  a.un = (float*)take(4 * a.B * D);
-  a.vn = (float*)take(4 * a.B * D);
-  a.unorm = (float*)take(4 * a.B);
-  a.vnorm = (float*)take(4 * a.B);
-  a.part_o = (float*)take(4 * a.chunks * a.B * D);
-  a.part_rs = (double*)take(8 * a.chunks * a.B);
-  a.cw = (float*)take(4 * a.B);
-  a.wv = (float*)take(4 * a.B);
-  a.row_loss = (double*)take(8 * a.B);
-}
-
-// F.normalize(x, dim=1): x / max(|x|, 1e-12); blockIdx.y: 0 users, 1 items
-template <int D>
-__global__ __launch_bounds__(256) void bs_prep(BsArgs a) {
-  constexpr int LPR = D / 4, RPB = 256 / LPR;
-  const bool item = blockIdx.y & 1;
-  const float* src = item ? a.v : a.u;
-  float* dst = item ? a.vn : a.un;
-  float* nrm_out = item ? a.vnorm : a.unorm;
-  const int64_t row = (int64_t)blockIdx.x * RPB + threadIdx.x / LPR;
-  const int lane = threadIdx.x % LPR;
-  const bool ok = row < a.B;
-  const float4 x = ok ? reinterpret_cast<const float4*>(src + row * D)[lane] : f4_zero();
-  const float nrm = sqrtf(group_sum<LPR>(f4_dot(x, x)));
-  const float den = fmaxf(nrm, kNormEps);
-  if (ok) {
-    reinterpret_cast<float4*>(dst + row * D)[lane] = make_float4(x.x / den, x.y / den, x.z / den, x.w / den);
-    if (lane == 0) nrm_out[row] = nrm;
-  }
-}
-
-// pass 1: R = users, C = a chunk of items, weight e = exp((s - 1) / tau)  -> per (chunk, user): sum e, sum e v_j
-// pass 2: R = items, C = all users, weight e cw_b - [b == j] w_b        -> dL/dv_j (normalisation backward fused)
-// (the rows are unit vectors: every logit is <= 1/tau and exp((s - 1)/tau) needs no running max)
-template <int D, bool PASS2>
-__global__ __launch_bounds__(256) void bs_pass(BsArgs a) {
-  constexpr int LDS_STRIDE = D + 4;
-  __shared__ float cs[kBsCTile * LDS_STRIDE];
-  __shared__ float cwt[kBsCTile];
-  __shared__ float cwd[kBsCTile];
-  const float* Rn = PASS2 ? a.vn : a.un;
-  const float* Cn = PASS2 ? a.un : a.vn;
-  const int64_t rtile = PASS2 ? (int64_t)blockIdx.x : (int64_t)blockIdx.x / a.chunks;
-  const int64_t chunk = PASS2 ? 0 : (int64_t)blockIdx.x % a.chunks;
-  int64_t cbeg = 0, cend = a.B;
-  if (!PASS2) {
-    cbeg = chunk * a.chunk_len;
-    cend = std::min(cbeg + a.chunk_len, a.B);
-  }
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, g = lane >> 4, j16 = lane & 15;
-  const int64_t r = rtile * kBsRows + wave * 16 + j16;
-  const bool rok = r < a.B;
-  const float inv_tau = a.inv_tau;
-  float rf[D / 4];
-#pragma unroll
-  for (int s = 0; s < D / 4; ++s) rf[s] = rok ? Rn[r * D + 4 * s + g] : 0.f;
-  f32x4 o[D / 16];
-#pragma unroll
-  for (int b = 0; b < D / 16; ++b) o[b] = f32x4{0.f, 0.f, 0.f, 0.f};
-  double rs = 0.0;
-
-  for (int64_t c0 = cbeg; c0 < cend; c0 += kBsCTile) {
-    __syncthreads();
-    for (int e = threadIdx.x; e < kBsCTile * (D / 4); e += 256) {
-      const int i = e / (D / 4), q = e % (D / 4);
-      const int64_t c = c0 + i;
-      *reinterpret_cast<float4*>(&cs[i * LDS_STRIDE + 4 * q]) =
-          c < cend ? reinterpret_cast<const float4*>(Cn + c * D)[q] : f4_zero();
-    }
-    if (threadIdx.x < kBsCTile) {
-      const int64_t c = c0 + threadIdx.x;
-      const bool cok = c < cend;
-      cwt[threadIdx.x] = cok ? (PASS2 ? a.cw[c] : 1.f) : 0.f;
-      cwd[threadIdx.x] = (PASS2 && cok) ? a.wv[c] : 0.f;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int sub = 0; sub < kBsCTile / 16; ++sub) {
-      f32x4 s = {0.f, 0.f, 0.f, 0.f};
-      const float* arow = &cs[(sub * 16 + j16) * LDS_STRIDE + g];
-#pragma unroll
-      for (int k = 0; k < D / 4; ++k) s = __builtin_amdgcn_mfma_f32_16x16x4f32(arow[4 * k], rf[k], s, 0, 0, 0);
-      // s[reg] = S^T[c = c0 + sub*16 + 4g + reg][r]
-#pragma unroll
-      for (int reg = 0; reg < 4; ++reg) {
-        const int ci = sub * 16 + 4 * g + reg;
-        float w = expf((s[reg] - 1.f) * inv_tau) * cwt[ci];
-        if (PASS2) {
-          if (c0 + ci == r) w -= cwd[ci];
-        } else {
-          rs += (double)w;
-        }
-        s[reg] = w;
-      }
-#pragma unroll
-      for (int b = 0; b < D / 16; ++b) {
-#pragma unroll
-        for (int reg = 0; reg < 4; ++reg)
-          o[b] = __builtin_amdgcn_mfma_f32_16x16x4f32(cs[(sub * 16 + 4 * g + reg) * LDS_STRIDE + 16 * b + j16], s[reg], o[b],
-                                                      0, 0, 0);
-      }
-    }
-  }
-  // o[b][reg] = O[r][16b + 4g + reg]
-  if (!PASS2) {
-    rs += __shfl_xor(rs, 16);
-    rs += __shfl_xor(rs, 32);
-    if (!rok) return;
-    const int64_t row = chunk * a.B + r;
-    if (g == 0) a.part_rs[row] = rs;
-#pragma unroll
-    for (int b = 0; b < D / 16; ++b)
-      reinterpret_cast<float4*>(a.part_o + row * D + 16 * b + 4 * g)[0] = make_float4(o[b][0], o[b][1], o[b][2], o[b][3]);
-  } else {
-    const float k = inv_tau / (float)a.B;
-    float4 tv[D / 16];
-    float dot = 0.f;
-#pragma unroll
-    for (int b = 0; b < D / 16; ++b) {
-      tv[b] = rok ? reinterpret_cast<const float4*>(a.vn + r * D + 16 * b + 4 * g)[0] : f4_zero();
-      o[b] *= k;
-      dot = fmaf(tv[b].x, o[b][0], fmaf(tv[b].y, o[b][1], fmaf(tv[b].z, o[b][2], fmaf(tv[b].w, o[b][3], dot))));
-    }
-    dot += __shfl_xor(dot, 16);
-    dot += __shfl_xor(dot, 32);
-    if (!rok) return;
-    const float nrm = a.vnorm[r];
-    const float inv = 1.f / fmaxf(nrm, kNormEps);
-    const bool clamped = !(nrm > kNormEps);
-#pragma unroll
-    for (int b = 0; b < D / 16; ++b) {
-      float4 out;
-      if (clamped) {
-        out = make_float4(o[b][0] * inv, o[b][1] * inv, o[b][2] * inv, o[b][3] * inv);
-      } else {
-        out = make_float4((o[b][0] - tv[b].x * dot) * inv, (o[b][1] - tv[b].y * dot) * inv,
-                          (o[b][2] - tv[b].z * dot) * inv, (o[b][3] - tv[b].w * dot) * inv);
-      }
-      reinterpret_cast<float4*>(a.gv + r * D + 16 * b + 4 * g)[0] = out;
-    }
-  }
-}
-
-// per user b: the chunk partials in chunk order -> row sum, p_b, loss term, w_b, dL/du_b
-template <int D>
-__global__ __launch_bounds__(256) void bs_finish(BsArgs a) {
-  constexpr int LPR = D / 4, RPB = 256 / LPR;
-  const int64_t b = (int64_t)blockIdx.x * RPB + threadIdx.x / LPR;
-  const int lane = threadIdx.x % LPR;
-  if (b >= a.B) return;  // (whole row groups leave together)
-  double rs = 0.0;
-  float4 o = f4_zero();
-  for (int64_t c = 0; c < a.chunks; ++c) {
-    rs += a.part_rs[c * a.B + b];
-    o = f4_add(o, reinterpret_cast<const float4*>(a.part_o + (c * a.B + b) * D)[lane]);
-  }
-  const float4 q = reinterpret_cast<const float4*>(a.un + b * D)[lane];
-  const float4 t = reinterpret_cast<const float4*>(a.vn + b * D)[lane];
-  const float spos = group_sum<LPR>(f4_dot(q, t));
-  const double p = exp(((double)spos - 1.0) * (double)a.inv_tau) / rs;
-  const double w = p / (p + kBsEps);
-  const float inv_rs = (float)(1.0 / rs);
-  if (lane == 0) {
-    a.row_loss[b] = -log(p + kBsEps);
-    a.cw[b] = (float)(w / rs);
-    a.wv[b] = (float)w;
-  }
-  // dL/du_b = w_b / (B tau) (O_b / rowsum - v_b), then the normalisation backward
-  const float k = (float)w * a.inv_tau / (float)a.B;
-  float4 gq = make_float4(k * (o.x * inv_rs - t.x), k * (o.y * inv_rs - t.y), k * (o.z * inv_rs - t.z),
-                          k * (o.w * inv_rs - t.w));
-  const float dot = group_sum<LPR>(f4_dot(q, gq));
-  const float nrm = a.unorm[b];
-  const float inv = 1.f / fmaxf(nrm, kNormEps);
-  if (nrm > kNormEps) gq = make_float4(gq.x - q.x * dot, gq.y - q.y * dot, gq.z - q.z * dot, gq.w - q.w * dot);
-  reinterpret_cast<float4*>(a.gu + b * D)[lane] = f4_scale(gq, inv);
-}
-
-// the mean of the per-row terms, summed in a fixed order
-__global__ __launch_bounds__(256) void bs_loss(BsArgs a) {
-  __shared__ double part[256];
-  double s = 0.0;
-  for (int64_t b = threadIdx.x; b < a.B; b += 256) s += a.row_loss[b];
-  part[threadIdx.x] = s;
-  __syncthreads();
-  for (int w = 128; w > 0; w >>= 1) {
-    if ((int)threadIdx.x < w) part[threadIdx.x] += part[threadIdx.x + w];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) a.loss[0] = part[0] / (double)a.B;
-}
-
-template <int D>
-srh_status_t launch_batch_softmax(BsArgs& a, hipStream_t st) {
-  constexpr int RPB = 256 / (D / 4);
-  const int64_t rtiles = (a.B + kBsRows - 1) / kBsRows;
-  bs_prep<D><<<dim3((unsigned)((a.B + RPB - 1) / RPB), 2), 256, 0, st>>>(a);
-  SRH_LAUNCH_CHECK();
-  bs_pass<D, false><<<(unsigned)(rtiles * a.chunks), 256, 0, st>>>(a);
-  SRH_LAUNCH_CHECK();
-  bs_finish<D><<<(unsigned)((a.B + RPB - 1) / RPB), 256, 0, st>>>(a);
-  SRH_LAUNCH_CHECK();
-  bs_pass<D, true><<<(unsigned)rtiles, 256, 0, st>>>(a);
-  SRH_LAUNCH_CHECK();
-  bs_loss<<<1, 256, 0, st>>>(a);
-  SRH_LAUNCH_CHECK();
-  return SRH_OK;
-}
-
 srh_status_t check_weights(const srh_tower_weights_t* w) {
   SRH_REQUIRE(w && w->d_w1 && w->d_b1 && w->d_w2 && w->d_b2, "tower: null weight tensor");
   return SRH_OK;
@@ -657,24 +399,6 @@ srh_status_t srh_rows_segment_sum_f32(const float* d_x, int64_t n_rows, int32_t 
                                                                       n_rows, n_table, d_out);
   SRH_LAUNCH_CHECK();
   return SRH_OK;
-}
-
-int64_t srh_batch_softmax_ws_bytes(int64_t B, int32_t d) {
-  if (B <= 0 || (d != 64 && d != 128)) return 0;
-  return bs_ws_bytes(B, d);
-}
-
-srh_status_t srh_batch_softmax_fwd_bwd(const float* d_u, const float* d_v, int64_t B, int32_t d, float tau,
-                                       double* d_loss, float* d_gu, float* d_gv, void* d_ws, void* stream) {
-  SRH_REQUIRE(d_u && d_v && d_loss && d_gu && d_gv && d_ws, "batch_softmax: null argument");
-  SRH_REQUIRE(B > 0 && B < (int64_t(1) << 31), "batch_softmax: bad B");
-  SRH_REQUIRE(d == 64 || d == 128, "batch_softmax: d=%d unsupported (64 or 128; narrower rows are zero-padded)", d);
-  SRH_REQUIRE(tau > 0.f && std::isfinite(tau), "batch_softmax: temperature must be positive");
-  BsArgs a{};
-  a.u = d_u; a.v = d_v; a.B = B; a.inv_tau = 1.f / tau; a.loss = d_loss; a.gu = d_gu; a.gv = d_gv;
-  bs_carve(a, static_cast<char*>(d_ws), d);
-  hipStream_t st = as_stream(stream);
-  return d == 64 ? launch_batch_softmax<64>(a, st) : launch_batch_softmax<128>(a, st);
 }
 
 }  // extern "C"

@@ -1012,7 +1012,7 @@ def batch_scatter(lists, pairs, d_full, col0, dl):
 
 
 # ---- NCL (model/graph/NCL.py): batch rows against a whole table, and the k-means of the E-step ----------------------
-TABLE_NCE_WIDTHS = (64, 128)                 # srh_table_nce_fwd_bwd / srh_kmeans_assign_f32 (narrower rows: zero-padded)
+TABLE_NCE_WIDTHS = (64, 128)                 # csrc/contrastive.hip / srh_kmeans_assign_f32 (narrower rows: zero-padded)
 
 
 def table_nce_ws(problems, d: int, device):
@@ -1259,9 +1259,8 @@ def knn_score_topk(mode, users, r_indptr, r_indices, n_items, nbr_ids, nbr_sims,
     return ids, sc, ws
 
 
-# ---- SSL4Rec: the MLP towers and batch_softmax_loss (csrc/ssl4rec.hip) ----------------------------------------------------
+# ---- SSL4Rec: the MLP towers (csrc/ssl4rec.hip) and batch_softmax_loss (csrc/contrastive.hip) --------------------------
 TOWER_IN, TOWER_HIDDEN, TOWER_OUT = 64, 1024, 128
-BATCH_SOFTMAX_WIDTHS = (64, 128)
 
 
 def _tower_weights(w1, b1, w2, b2):
@@ -1368,9 +1367,9 @@ def batch_softmax_fwd_bwd(u, v, tau, ws=None):
     if u.dim() != 2 or u.shape != v.shape:
         raise SelfrecHipError("batch_softmax: u and v must be 2-D of the same shape")
     B, d = int(u.shape[0]), int(u.shape[1])
-    w = padded_width(d, BATCH_SOFTMAX_WIDTHS)
+    w = padded_width(d, TABLE_NCE_WIDTHS)
     if w is None:
-        raise SelfrecHipError(f"batch_softmax: rows of {d} columns -- the kernel serves up to {BATCH_SOFTMAX_WIDTHS[-1]}")
+        raise SelfrecHipError(f"batch_softmax: rows of {d} columns -- the kernel serves up to {TABLE_NCE_WIDTHS[-1]}")
     up, vp = pad_cols(u.float(), w), pad_cols(v.float(), w)
     dev = u.device
     need = int(_lib.load().srh_batch_softmax_ws_bytes(B, w))
