@@ -12,6 +12,7 @@ import torch
 from oracle import selfrec_oracle as O
 from selfrec_amd import ops
 
+from . import spmm_ref as R
 from .counter_rng import counter_noise
 
 pytestmark = pytest.mark.gpu
@@ -478,6 +479,439 @@ def test_value_free_product_with_row_scaling(tiny_data):
     tx = torch.from_numpy(x).to(DEV)
     ops.spmm(g.adj, tx, out=y, epilogue=ops.make_epilogue(row_scale=g.dinv, scale_out=True))
     assert rel_err(y.cpu().numpy(), dinv[:, None] * want) < 2e-6
+
+
+# ---- every epilogue feature, at every width, against the float64 restatement of the header (tests/spmm_ref.py) ----
+# Tolerances are the restatement's per-element bounds (derived there, not measured): a three-entry row is held hundreds of
+# times tighter than a heavy row.  Every launch runs twice and must repeat bit for bit (fixed reduction order).
+EPI_STAMP = 17
+EPI_STAMP_BIG = (1 << 33) + 17          # > 2^31: a mark is live iff mark == (int32) stamp
+EPI_EPS = 0.2
+_U8 = [True] * 8
+
+
+def _bit(t, n=8):
+    return [k == t for k in range(n)]
+
+
+_AX = dict(alpha=0.25, n_add=2, add_scale=[0.5, 2.0])
+# (name, what the launch carries).  pattern: d_vals = NULL; n_prev / mean_div: MEAN; alpha / n_add / add_scale: AXPY; alias0:
+# addend 0 is the output; row_mark / col_mark / add_sparse: activity marks (add_sparse needs d_add_mark); stamp: *d_mark_stamp
+EPI_CASES = [
+    ("mean-prev0", dict(n_prev=0, mean_div=1.0)),
+    ("mean-prev1", dict(n_prev=1, mean_div=2.0)),
+    ("mean-prev3", dict(n_prev=3, mean_div=4.0)),
+    ("mean-prev8", dict(n_prev=8, mean_div=9.0)),
+    ("mean-prev3-div2.5", dict(n_prev=3, mean_div=2.5)),
+    ("mean-prev0-perturb", dict(n_prev=0, mean_div=1.0, perturb=True)),
+    ("mean-prev3-perturb", dict(n_prev=3, mean_div=4.0, perturb=True)),
+    ("mean-prev8-perturb-div2.5", dict(n_prev=8, mean_div=2.5, perturb=True)),
+    ("axpy-alpha-only", dict(alpha=0.25, n_add=0)),
+    ("axpy-add1", dict(alpha=0.5, n_add=1, add_scale=[0.3])),
+    ("axpy-add2", dict(alpha=0.5, n_add=2, add_scale=[0.3, -2.0])),
+    ("axpy-add0-aliases-out", dict(alpha=0.5, n_add=2, add_scale=[1.0, 0.25], alias0=True)),
+    ("axpy-alpha1-addends", dict(alpha=1.0, n_add=2, add_scale=[0.5, 2.0])),
+    ("scale-in-pattern", dict(pattern=True, scale_in=True)),
+    ("scale-in-values", dict(scale_in=True)),
+    ("scale-out", dict(scale_out=True)),
+    ("scale-in-out-pattern", dict(pattern=True, scale_in=True, scale_out=True)),
+    ("scale-in-out-values", dict(scale_in=True, scale_out=True)),
+    ("add-rowscale-01", dict(scale_in=True, add_rowscale=[True, False], **_AX)),
+    ("add-rowscale-10", dict(pattern=True, scale_in=True, add_rowscale=[False, True], **_AX)),
+    ("add-rowscale-11-scale-out", dict(scale_in=True, scale_out=True, add_rowscale=[True, True], **_AX)),
+    ("add-rowscale-01-no-scale-flags", dict(add_rowscale=[True, False], **_AX)),
+    ("prev-unscale-bit0", dict(pattern=True, scale_in=True, n_prev=8, mean_div=9.0, prev_unscale=_bit(0))),
+    ("prev-unscale-bit1", dict(pattern=True, scale_in=True, n_prev=8, mean_div=9.0, prev_unscale=_bit(1))),
+    ("prev-unscale-bit7", dict(scale_in=True, n_prev=8, mean_div=9.0, prev_unscale=_bit(7))),
+    ("prev-unscale-all", dict(pattern=True, scale_in=True, n_prev=8, mean_div=9.0, prev_unscale=_U8)),
+    ("prev-unscale-101-of-3", dict(pattern=True, scale_in=True, n_prev=3, mean_div=4.0, prev_unscale=[True, False, True])),
+    ("mean-scale-out", dict(pattern=True, scale_in=True, scale_out=True, n_prev=3, mean_div=4.0, prev_unscale=[True, False, True])),
+    ("mean-scale-out-values-axpy", dict(scale_out=True, n_prev=1, mean_div=2.0, prev_unscale=[True], add_rowscale=[False, True], **_AX)),
+    ("rowmark-mean", dict(row_mark=True, n_prev=3, mean_div=4.0)),
+    ("rowmark-mean-scaled-perturb", dict(row_mark=True, pattern=True, scale_in=True, scale_out=True, n_prev=3, mean_div=4.0,
+                                         prev_unscale=[True, True, False], perturb=True)),
+    ("rowmark-stamp>2^31", dict(row_mark=True, n_prev=1, mean_div=2.0, stamp=EPI_STAMP_BIG)),
+    ("colmark", dict(col_mark=True)),
+    ("colmark-rowmark-mean-scaled", dict(col_mark=True, row_mark=True, scale_in=True, n_prev=3, mean_div=4.0,
+                                         prev_unscale=[False, True, False])),
+    ("colmark-stamp>2^31", dict(col_mark=True, stamp=EPI_STAMP_BIG, **_AX)),
+    ("addmark-sparse-01", dict(add_sparse=[True, False], **_AX)),
+    ("addmark-sparse-10", dict(add_sparse=[False, True], **_AX)),
+    ("addmark-sparse-11", dict(add_sparse=[True, True], **_AX)),
+    ("addmark-sparse-11-rowscale-stamp>2^31", dict(pattern=True, scale_in=True, scale_out=True, add_sparse=[True, True],
+                                                  add_rowscale=[False, True], stamp=EPI_STAMP_BIG, **_AX)),
+    ("addmark-sparse-10-rowmark", dict(add_sparse=[False, True], row_mark=True, **_AX)),
+]
+# d = 8 / 16 / 32 (the thin kernels): what the header allows there -- no row scaling, no pattern, no ADAM
+THIN_CASES = [c for c in EPI_CASES if c[0] in ("mean-prev0", "mean-prev3", "mean-prev8", "mean-prev3-perturb", "axpy-alpha-only",
+                                               "axpy-add1", "axpy-add0-aliases-out", "rowmark-mean", "rowmark-stamp>2^31", "colmark",
+                                               "colmark-stamp>2^31", "addmark-sparse-01", "addmark-sparse-10", "addmark-sparse-11",
+                                               "addmark-sparse-10-rowmark")]
+
+
+def _t32(a):
+    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(DEV)
+
+
+def _mark32(live):
+    """live rows carry (int32) stamp = 17; the dead ones a mix of other values, 0 and 17 + 2^16 among them"""
+    dead = np.array([16, 0, 17 + (1 << 16), -17], dtype=np.int32)[np.arange(live.size) % 4]
+    return torch.from_numpy(np.where(live, np.int32(17), dead).astype(np.int32)).to(DEV)
+
+
+def _epi_env(d, split_len):
+    m = powerlaw_csr(3000, 3000, 40000, seed=23, heavy_rows=3, heavy_len=1500, empty_rows=40)
+    s = R.epilogue_inputs(m, d, seed=d)
+    heavy = np.argsort(np.diff(m.indptr))[-3:]
+    assert (s["r"] == 0).sum() >= 60 and (s["r"][heavy] == 0).sum() >= 1 and np.all(s["r"][np.diff(m.indptr) == 0] == 0)
+    dev = {k: _t32(s[k]) for k in ("x", "x_cols", "noise", "r")}
+    dev.update(add=[_t32(a) for a in s["add"]], prev=[_t32(p) for p in s["prev"]],
+               row_mark=_mark32(s["row_live"]), col_mark=_mark32(s["col_live"]), add_mark=_mark32(s["add_live"]))
+    return dict(m=m, host=s, dev=dev, csr=ops.DeviceCSR.from_scipy(m, split_len=split_len), n=m.shape[0], d=d)
+
+
+def _epi_scaled(c):
+    return any(c.get(k) for k in ("scale_in", "scale_out", "add_rowscale", "prev_unscale"))
+
+
+def _epi_kwargs(env, c, y, mean):
+    """make_epilogue's arguments of case c on the outputs y / mean"""
+    T, kw = env["dev"], {}
+    if _epi_scaled(c):
+        kw.update(row_scale=T["r"], scale_in=bool(c.get("scale_in")), scale_out=bool(c.get("scale_out")),
+                  prev_unscale=c.get("prev_unscale"), add_rowscale=c.get("add_rowscale"))
+    if "mean_div" in c:
+        kw.update(prev=T["prev"][:c["n_prev"]], mean_div=c["mean_div"], mean_out=mean)
+    if "alpha" in c:
+        kw.update(add=[y if (t == 0 and c.get("alias0")) else T["add"][t] for t in range(c["n_add"])],
+                  add_scale=c.get("add_scale", []), alpha=c["alpha"])
+    if c.get("perturb"):
+        kw.update(perturb_eps=EPI_EPS, noise=T["noise"])
+    if c.get("row_mark") or c.get("col_mark") or c.get("add_sparse"):
+        kw.update(mark_stamp=torch.tensor([c.get("stamp", EPI_STAMP)], dtype=torch.int64, device=DEV),
+                  row_mark=T["row_mark"] if c.get("row_mark") else None, col_mark=T["col_mark"] if c.get("col_mark") else None,
+                  add_mark=T["add_mark"] if c.get("add_sparse") else None, add_sparse=c.get("add_sparse"))
+    return kw
+
+
+def _epi_launch(env, c):
+    T, n, d = env["dev"], env["n"], env["d"]
+    y = T["add"][0].clone() if c.get("alias0") else torch.full((n, d), 7.0, device=DEV)
+    mean = torch.full((n, d), 7.0, device=DEV) if "mean_div" in c else None
+    ops.spmm(env["csr"], T["x_cols"] if c.get("col_mark") else T["x"], out=y, pattern=bool(c.get("pattern")),
+             epilogue=ops.make_epilogue(**_epi_kwargs(env, c, y, mean)))
+    return y, mean
+
+
+def _epi_ref(env, c, x=None, noise=True):
+    s, n, d = env["host"], env["n"], env["d"]
+    sent = np.full((n, d), 7.0)
+    x = (s["x_cols"] if c.get("col_mark") else s["x"]) if x is None else x
+    return R.epilogue_ref(
+        env["m"], x, vals_pattern=bool(c.get("pattern")), row_scale=s["r"] if _epi_scaled(c) else None,
+        scale_in=bool(c.get("scale_in")), scale_out=bool(c.get("scale_out")),
+        alpha=c["alpha"] if ("alpha" in c and (c["n_add"] or c["alpha"] != 1.0)) else None,
+        add=s["add"][:c.get("n_add", 0)], add_scale=c.get("add_scale", []), add_rowscale=c.get("add_rowscale"),
+        add_sparse=c.get("add_sparse"), add_live=s["add_live"], prev=s["prev"][:c.get("n_prev", 0)],
+        prev_unscale=c.get("prev_unscale"), mean_div=c.get("mean_div"), row_live=s["row_live"] if c.get("row_mark") else None,
+        col_live=s["col_live"] if c.get("col_mark") else None, y_before=s["add"][0] if c.get("alias0") else sent,
+        mean_before=sent, noise=s["noise"] if (c.get("perturb") and noise) else None, eps=EPI_EPS)
+
+
+def _check_epi_case(env, name, c, report):
+    what = f"{name} (d={env['d']})"
+    y, mean = _epi_launch(env, c)
+    y2, mean2 = _epi_launch(env, c)
+    assert torch.equal(y, y2) and (mean is None or torch.equal(mean, mean2)), f"{what}: two launches differ"
+    y64, mean64, by, bm = _epi_ref(env, c)
+    skip = None
+    if c.get("perturb"):
+        raw = _epi_ref(env, {**c, "scale_out": False}, noise=False)[0]          # the value whose sign the perturbation takes
+        if c.get("row_mark"):
+            raw = np.where(env["host"]["row_live"][:, None], raw, 1.0)
+        skip, under_cap = R.sign_ambiguous(raw)
+        report.append(f"{what}: {int(skip.sum())} sign-ambiguous elements skipped")
+        assert under_cap, f"{what}: {int(skip.sum())} sign-ambiguous elements"
+        assert np.all(y.cpu().numpy()[raw == 0] == 0), f"{what}: sign(0) = 0"
+    for got, want, bound, out in ((y, y64, by, "y"), (mean, mean64, bm, "mean_out")):
+        if got is None:
+            continue
+        bad, worst = R.violations(got.cpu().numpy(), want, bound, skip)
+        assert bad == 0, f"{what} {out}: {worst}"
+    if c.get("row_mark"):
+        dead = ~env["host"]["row_live"]
+        assert np.all(y.cpu().numpy()[dead] == 7.0) and (mean is None or np.all(mean.cpu().numpy()[dead] == 7.0)), what
+
+
+def _print_report(report):
+    if report:
+        print("\n".join(report))
+
+
+@pytest.mark.parametrize("split_len", [0, 64], ids=["split-default", "split-64"])
+@pytest.mark.parametrize("d", [64, 128, 256])
+def test_spmm_epilogue_cases_match_float64_restatement(d, split_len):
+    """MEAN, AXPY, the row-scaling masks and the activity marks of srh_spmm_epilogue_t, one launch per EPI_CASES entry, on a
+    3000-node power-law graph with three 1500-entry rows (default split: 3 segments each; split 64: 24, the row finished
+    by the last segment to arrive), 40 empty rows, and a row scale that is exactly 0 on 2 % of the rows (one heavy row
+    and the empty rows among them) -- each output element within the restatement's own bound."""
+    env, report = _epi_env(d, split_len), []
+    for name, c in EPI_CASES:
+        _check_epi_case(env, name, c, report)
+    _print_report(report)
+
+
+@pytest.mark.parametrize("d", [8, 16, 32])
+def test_thin_spmm_epilogue_cases_match_float64_restatement(d):
+    """The thin kernels (pair: d = 8, slice: d = 16 / 32) on the split-64 graph: MEAN, AXPY, row / column / addend marks
+    against the restatement; what the header does not serve there -- row scaling, ADAM, zero-padded rows -- is REFUSED,
+    not ignored, before any launch."""
+    env, report = _epi_env(d, 64), []
+    for name, c in THIN_CASES:
+        if c.get("perturb") and d % 32:
+            continue        # (PERTURB normalises over whole rows a multiple of 32 wide: narrower tables are slices, COUNTER_CASES)
+        _check_epi_case(env, name, c, report)
+    _print_report(report)
+    T, n = env["dev"], env["n"]
+    y, z = torch.full((n, d), 7.0, device=DEV), torch.full((n, d), 7.0, device=DEV)
+    coef = torch.tensor([1e-3, 1.0], device=DEV)
+    refused = {"scale_in": dict(row_scale=T["r"], scale_in=True), "scale_out": dict(row_scale=T["r"], scale_out=True),
+               "add_rowscale": dict(row_scale=T["r"], add=[T["add"][0]], add_scale=[1.0], add_rowscale=[True]),
+               "prev_unscale": dict(row_scale=T["r"], prev=[T["prev"][0]], mean_div=2.0, mean_out=z, prev_unscale=[True]),
+               "adam": dict(adam=dict(param=z, m=z.clone(), v=z.clone(), coef=coef)),
+               "d_valid": dict(perturb_eps=EPI_EPS, noise=T["noise"], d_valid=d - 2)}
+    for name, kw in refused.items():
+        with pytest.raises(ops.SelfrecHipError):
+            ops.spmm(env["csr"], T["x"], out=y, epilogue=ops.make_epilogue(**kw))
+        torch.cuda.synchronize()
+        assert float((y - 7.0).abs().max()) == 0 and float((z - 7.0).abs().max()) == 0, name
+
+
+@pytest.mark.parametrize("split_len", [0, 64], ids=["split-default", "split-64"])
+@pytest.mark.parametrize("d", [64, 128, 256])
+def test_spmm_prescaled_chains_match_true_float64_products(d, split_len):
+    """The chains the engine runs in the pre-scaled domain, END TO END against products with diag(r) P diag(r) in float64.
+    Forward: (SCALE_IN | SCALE_OUT) twice, then SCALE_IN + MEAN with both earlier layers un-scaled.  Backward: a value
+    product stored pre-scaled with two batch-sparse addends (one row-scaled), a pattern product, and the last one
+    accumulating into its own output.  The tolerance of a launch is its restatement bound plus the previous launch's
+    tolerance carried through |r| P |r| (the operator is non-negative)."""
+    env = _epi_env(d, split_len)
+    s, T, m, n, csr = env["host"], env["dev"], env["m"], env["n"], env["csr"]
+    r = s["r"].astype(np.float64)[:, None]
+    with np.errstate(divide="ignore"):
+        rinv = np.where(r > 0, 1.0 / np.where(r > 0, r, 1.0), 0.0)
+    P = m.astype(np.float64)
+    P.data[:] = 1.0
+    Ahat = sp.diags(r[:, 0]) @ P @ sp.diags(r[:, 0])
+
+    def held(got, want, tol, what):
+        bad, worst = R.violations(got.cpu().numpy(), want, tol / R.BOUND_FACTOR)
+        assert bad == 0, f"{what} (d={d}): {worst}"
+
+    # ---- forward ----
+    E = s["x"].astype(np.float64)
+    xs0 = (r * E).astype(np.float32)
+    t1 = Ahat @ E
+    t2 = Ahat @ t1
+    t3 = Ahat @ t2
+    tol0 = R.U32 * np.abs(xs0)
+    y1 = torch.full((n, d), 7.0, device=DEV)
+    y2, y3, mean = y1.clone(), y1.clone(), y1.clone()
+    for out, x_in in ((y1, _t32(xs0)), (y2, y1)):
+        ops.spmm(csr, x_in, out=out, pattern=True, epilogue=ops.make_epilogue(row_scale=T["r"], scale_in=True, scale_out=True))
+    ops.spmm(csr, y2, out=y3, pattern=True,
+             epilogue=ops.make_epilogue(row_scale=T["r"], scale_in=True, prev=[y1, y2], prev_unscale=[True, True], mean_div=3.0,
+                                        mean_out=mean))
+    c12 = dict(pattern=True, scale_in=True, scale_out=True)
+    b1 = _epi_ref(env, c12, x=r * E)[2]
+    tol1 = r * r * (P @ tol0) + R.BOUND_FACTOR * b1
+    b2 = _epi_ref(env, c12, x=r * t1)[2]
+    tol2 = r * r * (P @ tol1) + R.BOUND_FACTOR * b2
+    _, _, b3, b3m = R.epilogue_ref(m, r * t2, vals_pattern=True, row_scale=s["r"], scale_in=True, prev=[r * t1, r * t2],
+                                   prev_unscale=[True, True], mean_div=3.0)
+    tol3 = r * (P @ tol2) + R.BOUND_FACTOR * b3
+    tolm = (rinv * tol1 + rinv * tol2 + r * (P @ tol2)) / 3.0 + R.BOUND_FACTOR * b3m
+    held(y1, r * t1, tol1, "forward layer 1 (pre-scaled)")
+    held(y2, r * t2, tol2, "forward layer 2 (pre-scaled)")
+    held(y3, t3, tol3, "forward layer 3 (true)")
+    held(mean, (t1 + t2 + t3) / 3.0, tolm, "forward mean")
+    assert np.all(mean.cpu().numpy()[r[:, 0] == 0] == 0)               # an isolated node's rows are exactly 0
+    # ---- backward ----
+    L = s["add_live"][:, None].astype(np.float64)
+    a0, a1, G, acc0 = (t.astype(np.float64) for t in (s["add"][0], s["add"][1], s["x"], s["prev"][0]))
+    rows = np.repeat(np.arange(n), np.diff(m.indptr))
+    vals1 = (s["r"][rows] * s["r"][m.indices]).astype(np.float32)      # D^-1/2 A D^-1/2 as a value array (the chain's first)
+    A1 = sp.csr_matrix((vals1.astype(np.float64), m.indices, m.indptr), shape=m.shape)
+    csr1 = csr.with_values(_t32(vals1))
+    mk = dict(add_mark=T["add_mark"], mark_stamp=torch.tensor([EPI_STAMP], dtype=torch.int64, device=DEV))
+    h2, h1, g0 = torch.full((n, d), 7.0, device=DEV), torch.full((n, d), 7.0, device=DEV), T["prev"][0].clone()
+    ops.spmm(csr1, T["x"], out=h2, epilogue=ops.make_epilogue(
+        row_scale=T["r"], scale_out=True, alpha=0.5, add=T["add"], add_scale=[0.5, 1.0], add_rowscale=[False, True],
+        add_sparse=[True, True], **mk))
+    ops.spmm(csr, h2, out=h1, pattern=True, epilogue=ops.make_epilogue(
+        row_scale=T["r"], scale_in=True, scale_out=True, add=[T["add"][0]], add_scale=[0.5], add_sparse=[True], **mk))
+    ops.spmm(csr, h1, out=g0, pattern=True, epilogue=ops.make_epilogue(
+        row_scale=T["r"], scale_in=True, add=[g0, T["add"][1]], add_scale=[1.0, 1.0], add_rowscale=[False, True],
+        add_sparse=[False, True], **mk))
+    H2 = 0.5 * (A1 @ G) + 0.5 * L * a0 + r * L * a1
+    H1 = Ahat @ H2 + 0.5 * L * a0
+    G0 = Ahat @ H1 + acc0 + r * L * a1
+    live = s["add_live"]
+    bA = R.epilogue_ref(A1, s["x"], row_scale=s["r"], scale_out=True, alpha=0.5, add=s["add"], add_scale=[0.5, 1.0],
+                        add_rowscale=[False, True], add_sparse=[True, True], add_live=live)[2]
+    tolA = R.BOUND_FACTOR * bA
+    bB = R.epilogue_ref(m, r * H2, vals_pattern=True, row_scale=s["r"], scale_in=True, scale_out=True, alpha=1.0, add=s["add"][:1],
+                        add_scale=[0.5], add_sparse=[True], add_live=live)[2]
+    tolB = r * r * (P @ tolA) + R.BOUND_FACTOR * bB
+    bC = R.epilogue_ref(m, r * H1, vals_pattern=True, row_scale=s["r"], scale_in=True, alpha=1.0, add=[s["prev"][0], s["add"][1]],
+                        add_scale=[1.0, 1.0], add_rowscale=[False, True], add_sparse=[False, True], add_live=live)[2]
+    tolC = r * (P @ tolB) + R.BOUND_FACTOR * bC
+    held(h2, r * H2, tolA, "backward product 1 (pre-scaled)")
+    held(h1, r * H1, tolB, "backward product 2 (pre-scaled)")
+    held(g0, G0, tolC, "backward product 3 (accumulated, true)")
+
+
+ADAM_HYPER = tuple(float(np.float32(c)) for c in (1e-3, 0.9, 0.999, 1e-8))       # lr, beta1, beta2, eps as the C ABI carries them
+_ADAM_AX = dict(alpha=0.25, n_add=2, add_scale=[0.25, 1.0])
+ADAM_CASES = [
+    ("adam-step7-sparse11-clear2-cursor", dict(step=7, add_sparse=[True, True], n_clear=2, cursor=True, **_ADAM_AX)),
+    ("adam-step1-dense-clear0", dict(step=1, n_clear=0, cursor=False, **_ADAM_AX)),
+    ("adam-step100000-scale-in-pattern-clear4-cursor", dict(step=100000, pattern=True, scale_in=True, add_rowscale=[False, True],
+                                                            add_sparse=[True, False], n_clear=4, cursor=True, **_ADAM_AX)),
+    ("adam-step7-scale-in-values-clear2", dict(step=7, scale_in=True, add_sparse=[True, True], n_clear=2, cursor=False, **_ADAM_AX)),
+    ("adam-step1-alpha-only-cursor", dict(step=1, alpha=0.25, n_add=0, n_clear=0, cursor=True)),
+    ("adam-step100000-sparse01-clear2-stamp>2^31", dict(step=100000, add_sparse=[False, True], n_clear=2, cursor=False,
+                                                       stamp=EPI_STAMP_BIG, **_ADAM_AX)),
+]
+
+
+def _adam_launch(env, c):
+    """one SRH_EPI_ADAM launch on fresh state -> dict of the tensors it may touch"""
+    a, n, d = env["adam"], env["n"], env["d"]
+    lr, b1, b2, eps = ADAM_HYPER
+    st = dict(p=_t32(a["p"]), m=_t32(a["m"]), v=_t32(a["v"]), y=torch.full((n, d), 7.0, device=DEV),
+              add=[_t32(t) for t in a["add"]], extra=[_t32(t) for t in env["host"]["prev"][:2]],
+              cursor=torch.tensor([3, c["step"]], dtype=torch.int64, device=DEV))
+    coef = torch.tensor([lr / (1.0 - b1 ** c["step"]), (1.0 - b2 ** c["step"]) ** 0.5], dtype=torch.float32, device=DEV)
+    st["clear"] = (st["add"] + st["extra"])[:c["n_clear"]]
+    mark = _mark32(a["add_live"])
+    adam = dict(param=st["p"], m=st["m"], v=st["v"], coef=coef, beta1=b1, beta2=b2, eps=eps, clear=st["clear"],
+                clear_mark=mark if c["n_clear"] else None, cursor=st["cursor"] if c["cursor"] else None)
+    kw = dict(add=st["add"][:c["n_add"]], add_scale=c.get("add_scale", []), alpha=c["alpha"], adam=adam)
+    if c.get("scale_in"):
+        kw.update(row_scale=_t32(a["r"]), scale_in=True, add_rowscale=c.get("add_rowscale"))
+    if c.get("add_sparse") or c["n_clear"]:
+        kw.update(mark_stamp=torch.tensor([c.get("stamp", EPI_STAMP)], dtype=torch.int64, device=DEV))
+    if c.get("add_sparse"):
+        kw.update(add_mark=mark, add_sparse=c["add_sparse"])
+    ops.spmm(env["csr"], env["adam_x"], out=st["y"], pattern=bool(c.get("pattern")), epilogue=ops.make_epilogue(**kw))
+    torch.cuda.synchronize()
+    return st
+
+
+@pytest.mark.parametrize("split_len", [0, 64], ids=["split-default", "split-64"])
+@pytest.mark.parametrize("d", [64, 128, 256])
+def test_spmm_adam_epilogue_matches_float64_adam(d, split_len):
+    """SRH_EPI_ADAM against torch's formula in float64 (spmm_ref.adam_ref) fed the FLOAT64 gradient of the restatement: both
+    moments within their bounds; the parameter inside the hull of adam_ref at g -/+ bound_g, widened by 4 * 2^-24 (|p| +
+    |update|) -- sqrt(v_hat) is near eps-sized gradients on part of the table, so no blanket number; less than 1 % of the
+    hull may be wider than 1e-3 |update| (asserted: the check cannot go vacuous).  d_y keeps its sentinel, the tables to
+    clear are zero exactly on the marked rows, the cursor moves by one."""
+    env = _epi_env(d, split_len)
+    a = env["adam"] = R.adam_inputs(env["m"], d, seed=d)
+    env["adam_x"] = _t32(a["x"])
+    lr, b1, b2, eps = ADAM_HYPER
+    report = []
+    for name, c in ADAM_CASES:
+        what = f"{name} (d={d})"
+        st, st2 = _adam_launch(env, c), _adam_launch(env, c)
+        for k in ("p", "m", "v", "cursor"):
+            assert torch.equal(st[k], st2[k]), f"{what}: two launches differ in {k}"
+        g64, _, bg, _ = R.epilogue_ref(env["m"], a["x"], vals_pattern=bool(c.get("pattern")),
+                                       row_scale=a["r"] if c.get("scale_in") else None, scale_in=bool(c.get("scale_in")),
+                                       alpha=c["alpha"], add=a["add"][:c["n_add"]], add_scale=c.get("add_scale", []),
+                                       add_rowscale=c.get("add_rowscale"), add_sparse=c.get("add_sparse"), add_live=a["add_live"])
+        w = R.adam_bounds(a["p"], a["m"], a["v"], g64, bg, c["step"], lr, b1, b2, eps)
+        ill = float(w["ill"].mean())
+        report.append(f"{what}: ill-conditioned fraction {ill:.5f}")
+        assert ill < 0.01, what
+        for k in ("m", "v"):
+            bad, worst = R.violations(st[k].cpu().numpy(), w[k], w["bound_" + k])
+            assert bad == 0, f"{what} {k}: {worst}"
+        p = st["p"].cpu().numpy().astype(np.float64)
+        out = ~((p >= w["p_lo"]) & (p <= w["p_hi"]))
+        i = np.unravel_index(int(np.argmax(np.maximum(w["p_lo"] - p, p - w["p_hi"]))), p.shape)
+        assert not out.any(), f"{what} p: {int(out.sum())} outside the hull; at {i}: {p[i]!r} not in [{w['p_lo'][i]!r}, {w['p_hi'][i]!r}]"
+        e = a["empty"]                                             # g = 0, m0 = v0 = 0 exactly: 0 / (0 + eps), no move at all
+        assert np.all(g64[e] == 0) and np.array_equal(st["p"].cpu().numpy()[e], a["p"][e]), what
+        assert np.all(st["m"].cpu().numpy()[e] == 0) and np.all(st["v"].cpu().numpy()[e] == 0), what
+        assert float((st["y"] - 7.0).abs().max()) == 0, f"{what}: d_y was written"
+        assert st["cursor"].tolist() == ([4, c["step"] + 1] if c["cursor"] else [3, c["step"]]), what
+        live = a["add_live"]
+        before = a["add"] + env["host"]["prev"][:2]
+        for k, t in enumerate(st["add"] + st["extra"]):
+            got = t.cpu().numpy()
+            if k < c["n_clear"]:
+                assert np.all(got[live] == 0) and np.array_equal(got[~live], before[k][~live]), f"{what}: cleared table {k}"
+            else:
+                assert np.array_equal(got, before[k]), f"{what}: table {k} is not to be cleared"
+    _print_report(report)
+
+
+def test_spmm_epilogue_rejections_happen_before_any_launch():
+    """What the header promises to refuse: MEAN with mean_div = 0 or n_prev = 9; n_add = 3; marks without a stamp; an unknown
+    scale_flags bit; row scaling without d_row_scale; ADAM next to MEAN / SCALE_OUT / row marks / PERTURB, or with a table
+    that is the product's x.  Every output keeps its sentinel."""
+    env = _epi_env(64, 0)
+    T, n, d, csr = env["dev"], env["n"], 64, env["csr"]
+    y, mean = torch.full((n, d), 7.0, device=DEV), torch.full((n, d), 7.0, device=DEV)
+    p, mo, v = (torch.full((n, d), 7.0, device=DEV) for _ in range(3))
+    coef = torch.tensor([1e-3, 1.0], device=DEV)
+    stamp = torch.tensor([EPI_STAMP], dtype=torch.int64, device=DEV)
+    adam = dict(param=p, m=mo, v=v, coef=coef)
+    x_before = T["x"].clone()
+
+    def changed(ep, **fields):
+        for k, val in fields.items():
+            setattr(ep, k, val)
+        return ep
+    L = ops._lib
+    cases = {
+        "mean_div=0": lambda: ops.make_epilogue(prev=T["prev"][:2], mean_div=0.0, mean_out=mean),
+        "n_prev=9": lambda: changed(ops.make_epilogue(prev=T["prev"][:8], mean_div=9.0, mean_out=mean), n_prev=9),
+        "n_prev=-1": lambda: changed(ops.make_epilogue(prev=T["prev"][:8], mean_div=9.0, mean_out=mean), n_prev=-1),
+        "n_add=3": lambda: changed(ops.make_epilogue(add=T["add"], add_scale=[1.0, 1.0]), n_add=3),
+        "row_mark without stamp": lambda: ops.make_epilogue(row_mark=T["row_mark"]),
+        "col_mark without stamp": lambda: ops.make_epilogue(col_mark=T["col_mark"]),
+        "add_mark without stamp": lambda: ops.make_epilogue(add=T["add"], add_scale=[1.0, 1.0], add_mark=T["add_mark"], add_sparse=[True, True]),
+        "unknown scale flag": lambda: changed(ops.make_epilogue(row_scale=T["r"], scale_in=True), scale_flags=L.SRH_SCALE_IN | 4),
+        "unknown epilogue flag": lambda: changed(ops.make_epilogue(alpha=0.5), flags=L.SRH_EPI_AXPY | 16),
+        "SCALE_IN without d_row_scale": lambda: changed(ops.make_epilogue(alpha=0.5), scale_flags=L.SRH_SCALE_IN),
+        "prev_unscale without d_row_scale": lambda: changed(ops.make_epilogue(prev=T["prev"][:1], mean_div=2.0, mean_out=mean), prev_unscale_mask=1),
+        "add_rowscale without d_row_scale": lambda: changed(ops.make_epilogue(add=T["add"], add_scale=[1.0, 1.0]), add_rowscale_mask=2),
+        "ADAM + MEAN": lambda: ops.make_epilogue(prev=T["prev"][:1], mean_div=2.0, mean_out=mean, adam=adam),
+        "ADAM + SCALE_OUT": lambda: ops.make_epilogue(row_scale=T["r"], scale_out=True, adam=adam),
+        "ADAM + PERTURB": lambda: ops.make_epilogue(perturb_eps=0.1, noise=T["noise"], adam=adam),
+        "ADAM + row marks": lambda: ops.make_epilogue(row_mark=T["row_mark"], mark_stamp=stamp, adam=adam),
+        "ADAM + column marks": lambda: ops.make_epilogue(col_mark=T["col_mark"], mark_stamp=stamp, adam=adam),
+        "ADAM param is x": lambda: ops.make_epilogue(adam=dict(adam, param=T["x"])),
+        "ADAM m is x": lambda: ops.make_epilogue(adam=dict(adam, m=T["x"])),
+        "ADAM v is x": lambda: ops.make_epilogue(adam=dict(adam, v=T["x"])),
+        "ADAM clears x": lambda: ops.make_epilogue(mark_stamp=stamp, adam=dict(adam, clear=[T["x"]], clear_mark=T["add_mark"])),
+        "ADAM clear without marks": lambda: ops.make_epilogue(mark_stamp=stamp, adam=dict(adam, clear=[T["add"][0].clone()])),
+        "ADAM without coef": lambda: changed(ops.make_epilogue(adam=adam), d_adam_coef=None),
+    }
+    for name, make in cases.items():
+        with pytest.raises(ops.SelfrecHipError):
+            ops.spmm(csr, T["x"], out=y, epilogue=make())
+        torch.cuda.synchronize()
+        for t in (y, mean, p, mo, v):
+            assert float((t - 7.0).abs().max()) == 0, name
+        assert torch.equal(T["x"], x_before), name
+    with pytest.raises(ops.SelfrecHipError):                      # a pattern product takes no column marks
+        ops.spmm(csr, T["x_cols"], out=y, pattern=True, epilogue=ops.make_epilogue(col_mark=T["col_mark"], mark_stamp=stamp))
+    torch.cuda.synchronize()
+    assert float((y - 7.0).abs().max()) == 0
 
 
 @pytest.mark.selfcheck
