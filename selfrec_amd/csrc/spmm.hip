@@ -98,17 +98,55 @@ struct DevEpilogue {
 
 // Counter-based noise: lowbias32 / counter_rng4 / u01 (common.h).
 
-// Epilogue on one full row held as float4 per lane of an LPR-lane group.  Executed by all
-// groups of the wave with identical data (they all hold the reduced row); `store` selects
-// the group that writes.
-// Partials another XCD published with a write-through store are read with agent-scope (sc1) loads: coherence per
-// access.  An acquire FENCE instead (buffer_inv sc1) drops the whole XCD L2 -- thousands of them per launch were
-// costing the x rows their hit rate.
-// The partial sums of a split row, added in slot order by the segment that arrived last: partials t0, t0 + step, ...
-// (< hn) of this lane's 16 bytes.  Eight 16-byte agent-scope loads are in flight before the first add (one
-// global_load_dwordx4 sc1 each; 16-byte sc1 accesses are observed untorn on gfx950, MI355X_MICROARCH.md): the plain loop
-// -- four dword loads, wait, add, per partial -- put up to 30 dependent round trips at the end of the heaviest rows, which
-// is the critical path of the batch-masked launches (profiles/r02_i_wave_timeline_*).  Same order of additions.
+// ---- the split-row hand-off (every product kernel, and tools/spmm_lab) -------------------------------------------
+// A row longer than split_len is cut into segments, one wave each, and finished inside the launch by whichever of its
+// segments arrives last:
+//   1. every segment publishes its partial sum with WRITE-THROUGH (sc1) stores: the bytes go straight to memory and are not
+//      left dirty in this XCD's L2, so publishing needs no L2 write-back fence (cdna_hip_programming.md G16, form R1);
+//   2. split_arrive waits for those stores (vmcnt(0)) and takes a relaxed agent-scope ticket of the row; the wave that
+//      draws the last one re-arms the ticket for the next launch and owns the finish;
+//   3. it reads all partials with agent-scope (sc1) loads -- coherence per access.  An acquire FENCE instead (buffer_inv
+//      sc1) drops the whole XCD L2: thousands of them per launch were costing the x rows their hit rate;
+//   4. it adds them in SLOT order, whichever segment came last: run-to-run bitwise reproducible (partials t0, t0 + step, ..
+//      per row-group, then SRH_GROUPS_SUM over the groups), and runs the epilogue.
+typedef float floatx4_t __attribute__((ext_vector_type(4)));
+// (s_nop 1 after the 16-byte store: see st_f4, common.h)
+__device__ __forceinline__ void store_f4_sc1(float4* p, float4 v) {
+  floatx4_t x = {v.x, v.y, v.z, v.w};
+  asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" ::"v"(p), "v"(x) : "memory");
+}
+__device__ __forceinline__ void store_f_sc1(float* p, float v) {
+  asm volatile("global_store_dword %0, %1, off sc1" ::"v"(p), "v"(v) : "memory");
+}
+
+// Step 2 of the list above, for the whole wave, AFTER it has issued the write-through stores of its partial (slot SLOT).
+// Declares FIRST and N (the row's partial slots FIRST .. FIRST + N - 1, wave-uniform); a wave that did not arrive last
+// executes NOT_LAST, which must leave the kernel.  Use it once per block, as a full statement (it is several statements and
+// declares locals).  A macro, not a function: every function shape tried (bool + references, a returned struct, a
+// continuation) moved instructions or registers in the kernels' gather loops.
+#define SRH_SPLIT_ARRIVE(SLOT, LANE, HEAVY, SLOT_OWNER, TICKETS, FIRST, N, NOT_LAST)                                       \
+  const int srh_hid_ = __builtin_amdgcn_readfirstlane((SLOT_OWNER)[SLOT]);                                                 \
+  const Heavy srh_heavy_ = (HEAVY)[srh_hid_];                                                                              \
+  const int FIRST = __builtin_amdgcn_readfirstlane(srh_heavy_.first_slot);                                                 \
+  const int N = __builtin_amdgcn_readfirstlane(srh_heavy_.n_slots);                                                        \
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); /* this wave's write-through stores have landed */                     \
+  int srh_ticket_ = 0;                                                                                                     \
+  if ((LANE) == 0)                                                                                                         \
+    srh_ticket_ = __hip_atomic_fetch_add((TICKETS) + srh_hid_, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);             \
+  srh_ticket_ = __builtin_amdgcn_readfirstlane(srh_ticket_);                                                               \
+  if (srh_ticket_ != N - 1) NOT_LAST;                                                                                      \
+  if ((LANE) == 0) __hip_atomic_store((TICKETS) + srh_hid_, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) /* re-arm */
+
+// Sum / maximum of V over the 64 / LPR row-groups of a wave: afterwards every group holds the whole wave's total, lane position
+// by lane position (group_sum, common.h, reduces INSIDE a group).  Macros for the same reason as SRH_SPLIT_ARRIVE.
+#define SRH_GROUPS_SUM(LPR, V) _Pragma("unroll") for (int m_ = (LPR); m_ < 64; m_ <<= 1) V = f4_add(V, f4_shfl_xor(V, m_))
+#define SRH_GROUPS_MAX(LPR, V) _Pragma("unroll") for (int m_ = (LPR); m_ < 64; m_ <<= 1) V = max(V, __shfl_xor(V, m_))
+
+// Partials t0, t0 + step, ... (< hn) of this lane's 16 bytes, added in that order.  Eight 16-byte agent-scope loads are in
+// flight before the first add (one global_load_dwordx4 sc1 each; 16-byte sc1 accesses are observed untorn on gfx950,
+// MI355X_MICROARCH.md): the plain loop -- four dword loads, wait, add, per partial -- put up to 30 dependent round trips at
+// the end of the heaviest rows, which is the critical path of the batch-masked launches (profiles/r02_i_wave_timeline_*).
+// Same order of additions.
 __device__ __forceinline__ float4 sum_partials_agent(const float4* base, int t0, int step, int hn, int stride4) {
   typedef float fx4 __attribute__((ext_vector_type(4)));
   float4 sum = f4_zero();
@@ -186,6 +224,8 @@ __device__ __forceinline__ float4 perturb_row(float4 y, int row, int sub, size_t
   return y;
 }
 
+// Epilogue on one full row held as float4 per lane of an LPR-lane group.  Executed by all groups of the wave with identical
+// data (they all hold the reduced row); `store` selects the group that writes.
 // r: the row's scale factor (1 when the launch has none) -- loaded by the caller BEFORE its gathers: these waves run on
 // their chain of dependent round trips, and a load issued here would add one to every row
 template <int LPR, bool ADAM = false>
@@ -269,8 +309,6 @@ __device__ __forceinline__ void row_epilogue(float4 y, int row, int sub, bool st
 //   * one wave per long row / split segment ("coop" tasks): each row-group takes a block of 16 entries of a
 //     16*G-entry chunk and the groups are summed at the end.
 // ---------------------------------------------------------------------------------------------
-typedef float floatx4_t __attribute__((ext_vector_type(4)));
-
 struct Task {
   int32_t kind, first, count, pad;   // kind 0: coop on segs[first]; kind 1: rows segs[first .. first+count)
 };
@@ -287,13 +325,6 @@ template <int LPR>
 __device__ __forceinline__ float4 ld_x(const float4* __restrict__ X, int c, int sub) {
   const unsigned off = (unsigned)c * (unsigned)(LPR * 16) + (unsigned)(sub * 16);
   return *reinterpret_cast<const float4*>(reinterpret_cast<const char*>(X) + off);
-}
-
-// 16-byte write-through store (sc1): the partial goes straight to memory and is not left dirty in this
-// XCD's L2, so publishing it needs no L2 write-back fence (cdna_hip_programming.md G16, form R1)
-__device__ __forceinline__ void store_f4_sc1(float4* p, float4 v) {
-  floatx4_t x = {v.x, v.y, v.z, v.w};
-  asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" ::"v"(p), "v"(x) : "memory");   // (nop: see st_f4, common.h)
 }
 
 // ---- the gather loop of spmm_rows_kernel, in inline assembly -------------------------------------------
@@ -641,27 +672,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
       leave();
       return;
     }
-#pragma unroll
-    for (int m = LPR; m < 64; m <<= 1) a4 = f4_add(a4, f4_shfl_xor(a4, m));
+    SRH_GROUPS_SUM(LPR, a4);
     if (slot < 0) {
       row_epilogue<LPR, ADAM>(a4, row, sub, g == 0, Y, ep, r);
       leave();
       return;
     }
     if (g == 0) store_f4_sc1(partial + (size_t)slot * LPR + sub, a4);
-    const int hid = __builtin_amdgcn_readfirstlane(slot_owner[slot]);
-    const Heavy h = heavy[hid];
-    const int hfirst = __builtin_amdgcn_readfirstlane(h.first_slot);
-    const int hn = __builtin_amdgcn_readfirstlane(h.n_slots);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // this wave's write-through stores have landed
-    int ticket = 0;
-    if (lane == 0) ticket = __hip_atomic_fetch_add(tickets + hid, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    ticket = __builtin_amdgcn_readfirstlane(ticket);
-    if (ticket != hn - 1) { leave(); return; }
-    if (lane == 0) __hip_atomic_store(tickets + hid, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // re-arm
-    float4 sum = sum_partials_agent(partial + (size_t)hfirst * LPR + sub, g, G, hn, LPR);
-#pragma unroll
-    for (int m = LPR; m < 64; m <<= 1) sum = f4_add(sum, f4_shfl_xor(sum, m));
+    SRH_SPLIT_ARRIVE(slot, lane, heavy, slot_owner, tickets, first, n, { leave(); return; });
+    float4 sum = sum_partials_agent(partial + (size_t)first * LPR + sub, g, G, n, LPR);
+    SRH_GROUPS_SUM(LPR, sum);
     row_epilogue<LPR, ADAM>(sum, row, sub, g == 0, Y, ep, r);
     leave();
     return;
@@ -675,8 +695,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
   const float r = ep.row_scale ? ep.row_scale[row] : 1.0f;
   if (!live) e = s;
   int maxlen = e - s;
-#pragma unroll
-  for (int m = LPR; m < 64; m <<= 1) maxlen = max(maxlen, __shfl_xor(maxlen, m));
+  SRH_GROUPS_MAX(LPR, maxlen);
   maxlen = __builtin_amdgcn_readfirstlane(maxlen);
   fetch(short_at(0, maxlen), e, cs, v);
   if (LATE) {
@@ -768,8 +787,7 @@ __global__ __launch_bounds__(256) void spmm_rows3_kernel(const Task* __restrict_
     }
 #pragma unroll
     for (int v = 0; v < 3; ++v)
-#pragma unroll
-      for (int m = LPR; m < 64; m <<= 1) acc[v] = f4_add(acc[v], f4_shfl_xor(acc[v], m));
+      SRH_GROUPS_SUM(LPR, acc[v]);
     if (slot < 0) {
       if (g == 0) {
 #pragma unroll
@@ -781,21 +799,11 @@ __global__ __launch_bounds__(256) void spmm_rows3_kernel(const Task* __restrict_
 #pragma unroll
       for (int v = 0; v < 3; ++v) store_f4_sc1(partial + (size_t)slot * 64 + v * LPR + sub, acc[v]);
     }
-    const int hid = __builtin_amdgcn_readfirstlane(slot_owner[slot]);
-    const Heavy h = heavy[hid];
-    const int hfirst = __builtin_amdgcn_readfirstlane(h.first_slot);
-    const int hn = __builtin_amdgcn_readfirstlane(h.n_slots);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    int ticket = 0;
-    if (lane == 0) ticket = __hip_atomic_fetch_add(tickets + hid, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    ticket = __builtin_amdgcn_readfirstlane(ticket);
-    if (ticket != hn - 1) return;
-    if (lane == 0) __hip_atomic_store(tickets + hid, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    SRH_SPLIT_ARRIVE(slot, lane, heavy, slot_owner, tickets, hfirst, hn, return);
 #pragma unroll
     for (int v = 0; v < 3; ++v) {
       float4 sum = sum_partials_agent(partial + (size_t)hfirst * 64 + v * LPR + sub, g, G, hn, 64);
-#pragma unroll
-      for (int m = LPR; m < 64; m <<= 1) sum = f4_add(sum, f4_shfl_xor(sum, m));
+      SRH_GROUPS_SUM(LPR, sum);
       if (g == 0) Y[v][(size_t)row * LPR + sub] = sum;
     }
     return;
@@ -807,8 +815,7 @@ __global__ __launch_bounds__(256) void spmm_rows3_kernel(const Task* __restrict_
   const int row = sg.row, s = sg.start;
   const int e = have ? sg.end : s;
   int maxlen = e - s;
-#pragma unroll
-  for (int m = LPR; m < 64; m <<= 1) maxlen = max(maxlen, __shfl_xor(maxlen, m));
+  SRH_GROUPS_MAX(LPR, maxlen);
   maxlen = __builtin_amdgcn_readfirstlane(maxlen);
   for (int q = 0; q * 16 < maxlen; ++q) {
     const int j = s + 16 * q + e16;
@@ -828,67 +835,24 @@ __global__ __launch_bounds__(256) void spmm_rows3_kernel(const Task* __restrict_
 // Column slices: the column-sharded multi-GPU layout keeps DL = d / G columns of every
 // (N, d) table on each rank, so a propagation layer needs no exchange at all -- the product is independent per
 // column -- and a gathered x row is only DL * 4 = 32 .. 128 bytes.  The helpers below serve the 8-column kernel
-// (spmm_pair_kernel): vector loads / stores of EPL = DL / 8 floats, the perturbation and the epilogue on a lane
-// that ends up holding EPL columns of a finished row.
+// (spmm_pair_kernel): the perturbation and the epilogue on a lane that ends up holding ONE column of a finished
+// row (16- and 32-column slices go through row_epilogue).
 // The PERTURB unit vector is normalised over the whole d-wide row (XSimGCL.py:90): with the counter RNG every
 // rank regenerates the row's other columns (hash only, no memory), with injected noise it reads the full noise
-// row; its own columns use exactly the counters of the one-GPU kernel, so a sharded run sees the same
+// row; its own column uses exactly the counter of the one-GPU kernel, so a sharded run sees the same
 // perturbation as an unsharded one.
 // ---------------------------------------------------------------------------------------------
-template <int EPL> struct ThinVec;
-template <> struct ThinVec<1> { using type = float; };
-template <> struct ThinVec<2> { using type = float2; };
-template <> struct ThinVec<4> { using type = float4; };
-
-template <int EPL>
-__device__ __forceinline__ void ld_epl(const float* p, float (&v)[EPL]) {
-  using V = typename ThinVec<EPL>::type;
-  union { V vec; float f[EPL]; } u;
-  u.vec = *reinterpret_cast<const V*>(p);
-#pragma unroll
-  for (int i = 0; i < EPL; ++i) v[i] = u.f[i];
-}
-template <int EPL>
-__device__ __forceinline__ void st_epl(float* p, const float (&v)[EPL]) {
-  using V = typename ThinVec<EPL>::type;
-  union { V vec; float f[EPL]; } u;
-#pragma unroll
-  for (int i = 0; i < EPL; ++i) u.f[i] = v[i];
-  *reinterpret_cast<V*>(p) = u.vec;
-}
-// write-through (sc1) store of a partial: not left dirty in this XCD's L2 (see store_f4_sc1)
-template <int EPL>
-__device__ __forceinline__ void st_epl_sc1(float* p, const float (&v)[EPL]) {
-  if constexpr (EPL == 1) {
-    asm volatile("global_store_dword %0, %1, off sc1" ::"v"(p), "v"(v[0]) : "memory");
-  } else if constexpr (EPL == 2) {
-    typedef float floatx2_t __attribute__((ext_vector_type(2)));
-    floatx2_t x = {v[0], v[1]};
-    asm volatile("global_store_dwordx2 %0, %1, off sc1" ::"v"(p), "v"(x) : "memory");
-  } else {
-    floatx4_t x = {v[0], v[1], v[2], v[3]};
-    asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" ::"v"(p), "v"(x) : "memory");
-  }
-}
-template <int EPL>
-__device__ __forceinline__ void ld_epl_agent(const float* p, float (&v)[EPL]) {
-#pragma unroll
-  for (int i = 0; i < EPL; ++i) v[i] = __hip_atomic_load(p + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
 __device__ __forceinline__ float pick4(uint4 r, int comp) {
   const uint32_t w = (comp == 0) ? r.x : (comp == 1) ? r.y : (comp == 2) ? r.z : r.w;
   return u01(w);
 }
 
-template <int DL>
-__device__ __forceinline__ void thin_perturb(float (&y)[DL / 8], const float (&raw)[DL / 8], int row, int el,
-                                             const float* noise, uint32_t off_lo, uint32_t off_hi,
-                                             const DevEpilogue& ep) {
-  constexpr int EPL = DL / 8;
+// raw + sign(raw) * normalize(noise_row) * eps on column `el` of the 8-column slice
+__device__ __forceinline__ float thin_perturb(float raw, int row, int el, const float* noise, uint32_t off_lo,
+                                              uint32_t off_hi, const DevEpilogue& ep) {
   const int dfull = ep.noise_d_full;
-  const int e0 = ep.noise_col0 + el * EPL;          // first of this lane's columns in the whole row
-  float nu[EPL];
+  const int e0 = ep.noise_col0 + el;                // this lane's column in the whole row
+  float nu;
   float ss = 0.f;
   if (noise) {
     const float* nr = noise + (size_t)row * dfull;
@@ -897,8 +861,7 @@ __device__ __forceinline__ void thin_perturb(float (&y)[DL / 8], const float (&r
       const float4 z = *reinterpret_cast<const float4*>(nr + el * per + t);
       ss += f4_dot(z, z);
     }
-#pragma unroll
-    for (int i = 0; i < EPL; ++i) nu[i] = nr[e0 + i];
+    nu = nr[e0];
   } else {
     uint64_t ctr = (((uint64_t)off_hi << 32) | off_lo) + (uint64_t)row;
     if (ep.rng_step) ctr += (uint64_t)(*ep.rng_step) * ep.rng_stride;
@@ -907,59 +870,42 @@ __device__ __forceinline__ void thin_perturb(float (&y)[DL / 8], const float (&r
       const float4 z = make_float4(u01(r.x), u01(r.y), u01(r.z), u01(r.w));
       ss += f4_dot(z, z);
     }
-    const uint4 r = counter_rng4(ctr, (uint32_t)(e0 >> 2), ep.seed_lo, ep.seed_hi);
-#pragma unroll
-    for (int i = 0; i < EPL; ++i) nu[i] = pick4(r, (e0 & 3) + i);
+    nu = pick4(counter_rng4(ctr, (uint32_t)(e0 >> 2), ep.seed_lo, ep.seed_hi), e0 & 3);
   }
   ss = group_sum<8>(ss);
   const float scale = ep.eps / fmaxf(sqrtf(ss), 1e-12f);
-#pragma unroll
-  for (int i = 0; i < EPL; ++i) y[i] = raw[i] + sgnf(raw[i]) * (nu[i] * scale);
+  return raw + sgnf(raw) * (nu * scale);
 }
 
-template <int DL>
-__device__ __forceinline__ void thin_epilogue(float (&y)[DL / 8], int row, int el, bool store, float* __restrict__ Y,
+// el: which column of the slice this lane holds -- any bijection of 0..7 over the 8 lanes of a group
+__device__ __forceinline__ void thin_epilogue(float y, int row, int el, bool store, float* __restrict__ Y,
                                               const DevEpilogue& ep) {
-  // el: which EPL columns of the slice this lane holds -- any bijection of 0..7 over the 8 lanes of a group
-  constexpr int EPL = DL / 8;
-  const size_t at = (size_t)row * DL + el * EPL;
+  const size_t at = (size_t)row * 8 + el;
   if (ep.flags & SRH_EPI_AXPY) {
-#pragma unroll
-    for (int i = 0; i < EPL; ++i) y[i] *= ep.alpha;
+    y *= ep.alpha;
     const bool marked = !ep.add_mark || ep.add_mark[row] == (int)(*ep.mark_stamp);
     for (int t = 0; t < ep.n_add; ++t) {
       if (((ep.add_sparse >> t) & 1) && !marked) continue;
-      float a[EPL];
-      ld_epl<EPL>(ep.add[t] + at, a);
-#pragma unroll
-      for (int i = 0; i < EPL; ++i) y[i] = fmaf(ep.add_scale[t], a[i], y[i]);
+      y = fmaf(ep.add_scale[t], ep.add[t][at], y);
     }
   }
   if (ep.flags & SRH_EPI_PERTURB) {
-    float raw[EPL];
-#pragma unroll
-    for (int i = 0; i < EPL; ++i) raw[i] = y[i];
-    if (!ep.main_clean) thin_perturb<DL>(y, raw, row, el, ep.noise, ep.off_lo, ep.off_hi, ep);
+    const float raw = y;
+    if (!ep.main_clean) y = thin_perturb(raw, row, el, ep.noise, ep.off_lo, ep.off_hi, ep);
     for (int k = 0; k < ep.n_extra; ++k) {
-      float yk[EPL];
-      thin_perturb<DL>(yk, raw, row, el, ep.extra_noise[k], ep.extra_off_lo[k], ep.extra_off_hi[k], ep);
-      if (store) st_epl<EPL>(ep.extra_out[k] + at, yk);
+      const float yk = thin_perturb(raw, row, el, ep.extra_noise[k], ep.extra_off_lo[k], ep.extra_off_hi[k], ep);
+      if (store) ep.extra_out[k][at] = yk;
     }
   }
-  if (store) st_epl<EPL>(Y + at, y);
+  if (store) Y[at] = y;
   if (ep.flags & SRH_EPI_MEAN) {
-    float m[EPL];
-#pragma unroll
-    for (int i = 0; i < EPL; ++i) m[i] = 0.f;
+    float m = 0.f;
     for (int t = 0; t < ep.n_prev; ++t) {
-      float a[EPL];
-      ld_epl<EPL>(ep.prev[t] + at, a);
-#pragma unroll
-      for (int i = 0; i < EPL; ++i) m[i] = (t == 0) ? a[i] : m[i] + a[i];
+      const float a = ep.prev[t][at];
+      m = (t == 0) ? a : m + a;
     }
-#pragma unroll
-    for (int i = 0; i < EPL; ++i) m[i] = (ep.n_prev > 0 ? m[i] + y[i] : y[i]) * ep.mean_rcp;
-    if (store) st_epl<EPL>(ep.mean_out + at, m);
+    m = (ep.n_prev > 0 ? m + y : y) * ep.mean_rcp;
+    if (store) ep.mean_out[at] = m;
   }
 }
 
@@ -980,7 +926,7 @@ __device__ __forceinline__ void pair_task(const Task& tk, const Seg& sgl, const 
                                           float* __restrict__ Y, float* __restrict__ partial,
                                           const Heavy* __restrict__ heavy, const int32_t* __restrict__ slot_owner,
                                           int32_t* __restrict__ tickets, const DevEpilogue& ep, int stamp, int lane) {
-  constexpr int DL = 8;
+  constexpr int DL = 8;                                                    // columns of the slice = lanes per row-group
   const int g = lane >> 3, e8 = lane & 7, h = lane & 1, pg = e8 >> 1;     // group, lane in group, half, pair in group
   const bool b2 = (e8 & 4) != 0, b1 = (e8 & 2) != 0;
   const int el = h * 4 + (b2 ? 2 : 0) + (b1 ? 1 : 0);                      // the column this lane ends up with
@@ -1023,42 +969,29 @@ __device__ __forceinline__ void pair_task(const Task& tk, const Seg& sgl, const 
     const float keep = b1 ? a1 : a0, send = b1 ? a0 : a1;
     return keep + __shfl_xor(send, 2);
   };
-  float out[1];
 
   if (kind == 0) {
     const int row = __builtin_amdgcn_readfirstlane(sgl.row), s = __builtin_amdgcn_readfirstlane(sgl.start);
     const int e = __builtin_amdgcn_readfirstlane(sgl.end), slot = __builtin_amdgcn_readfirstlane(sgl.slot);
     if (ep.row_mark && ep.row_mark[row] != stamp) return;
     for (int base = s; base < e; base += 256) accumulate(base + (lane >> 1), 32, e);
-    out[0] = reduce4();
-    out[0] += __shfl_xor(out[0], 8);
-    out[0] += __shfl_xor(out[0], 16);
-    out[0] += __shfl_xor(out[0], 32);
+    float out = reduce4();
+    out += __shfl_xor(out, 8);
+    out += __shfl_xor(out, 16);
+    out += __shfl_xor(out, 32);
     if (slot < 0) {
-      thin_epilogue<DL>(out, row, el, g == 0, Y, ep);
+      thin_epilogue(out, row, el, g == 0, Y, ep);
       return;
     }
-    if (g == 0) st_epl_sc1<1>(partial + (size_t)slot * DL + el, out);
-    const int hid = __builtin_amdgcn_readfirstlane(slot_owner[slot]);
-    const Heavy hv = heavy[hid];
-    const int hfirst = __builtin_amdgcn_readfirstlane(hv.first_slot);
-    const int hn = __builtin_amdgcn_readfirstlane(hv.n_slots);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // this wave's write-through stores have landed
-    int ticket = 0;
-    if (lane == 0) ticket = __hip_atomic_fetch_add(tickets + hid, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    ticket = __builtin_amdgcn_readfirstlane(ticket);
-    if (ticket != hn - 1) return;
-    if (lane == 0) __hip_atomic_store(tickets + hid, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // re-arm
-    float sum[1] = {0.f};
-    for (int t = g; t < hn; t += 8) {
-      float pz[1];
-      ld_epl_agent<1>(partial + (size_t)(hfirst + t) * DL + el, pz);
-      sum[0] += pz[0];
-    }
-    sum[0] += __shfl_xor(sum[0], 8);
-    sum[0] += __shfl_xor(sum[0], 16);
-    sum[0] += __shfl_xor(sum[0], 32);
-    thin_epilogue<DL>(sum, row, el, g == 0, Y, ep);
+    if (g == 0) store_f_sc1(partial + (size_t)slot * DL + el, out);
+    SRH_SPLIT_ARRIVE(slot, lane, heavy, slot_owner, tickets, hfirst, hn, return);
+    float sum = 0.f;                                         // (one column per lane: 4-byte agent-scope loads, slot order)
+    for (int t = g; t < hn; t += 8)
+      sum += __hip_atomic_load(partial + (size_t)(hfirst + t) * DL + el, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    sum += __shfl_xor(sum, 8);
+    sum += __shfl_xor(sum, 16);
+    sum += __shfl_xor(sum, 32);
+    thin_epilogue(sum, row, el, g == 0, Y, ep);
     return;
   }
 
@@ -1068,8 +1001,7 @@ __device__ __forceinline__ void pair_task(const Task& tk, const Seg& sgl, const 
   const bool live = have && (!ep.row_mark || ep.row_mark[row] == stamp);
   const int e = live ? sgl.end : s;
   for (int base = s; __any(base < e); base += 32) accumulate(base + pg, 4, e);
-  out[0] = reduce4();
-  thin_epilogue<DL>(out, row, el, live, Y, ep);
+  thin_epilogue(reduce4(), row, el, live, Y, ep);
 }
 
 __global__ __launch_bounds__(256) void spmm_pair_kernel(const Task* __restrict__ tasks, int n_tasks,
@@ -1203,26 +1135,15 @@ __global__ __launch_bounds__(256) void spmm_slice_kernel(const Task* __restrict_
       for (int k = 0; k < KCH; ++k)
         if (base + 8 * G * k < e) slice_gather8<LPR>(cq[k], vq[k], X, sub, lane, acc);
     }
-#pragma unroll
-    for (int m = LPR; m < 64; m <<= 1) acc = f4_add(acc, f4_shfl_xor(acc, m));
+    SRH_GROUPS_SUM(LPR, acc);
     if (slot < 0) {
       row_epilogue<LPR>(acc, row, sub, g == 0, Y, ep);
       return;
     }
     if (g == 0) store_f4_sc1(partial + (size_t)slot * LPR + sub, acc);
-    const int hid = __builtin_amdgcn_readfirstlane(slot_owner[slot]);
-    const Heavy h = heavy[hid];
-    const int hfirst = __builtin_amdgcn_readfirstlane(h.first_slot);
-    const int hn = __builtin_amdgcn_readfirstlane(h.n_slots);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // this wave's write-through stores have landed
-    int ticket = 0;
-    if (lane == 0) ticket = __hip_atomic_fetch_add(tickets + hid, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    ticket = __builtin_amdgcn_readfirstlane(ticket);
-    if (ticket != hn - 1) return;
-    if (lane == 0) __hip_atomic_store(tickets + hid, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // re-arm
+    SRH_SPLIT_ARRIVE(slot, lane, heavy, slot_owner, tickets, hfirst, hn, return);
     float4 sum = sum_partials_agent(partial + (size_t)hfirst * LPR + sub, g, G, hn, LPR);
-#pragma unroll
-    for (int m = LPR; m < 64; m <<= 1) sum = f4_add(sum, f4_shfl_xor(sum, m));
+    SRH_GROUPS_SUM(LPR, sum);
     row_epilogue<LPR>(sum, row, sub, g == 0, Y, ep);
     return;
   }
@@ -1234,8 +1155,7 @@ __global__ __launch_bounds__(256) void spmm_slice_kernel(const Task* __restrict_
   const bool live = have && (!ep.row_mark || ep.row_mark[row] == stamp);
   const int e = live ? sg.end : s;
   int maxlen = e - s;
-#pragma unroll
-  for (int m = LPR; m < 64; m <<= 1) maxlen = max(maxlen, __shfl_xor(maxlen, m));
+  SRH_GROUPS_MAX(LPR, maxlen);
   maxlen = __builtin_amdgcn_readfirstlane(maxlen);
   for (int q0 = 0; q0 * 8 < maxlen; q0 += 8) {        // (one pass: short rows have at most 64 entries)
     int cq[8][NB];
@@ -1322,6 +1242,18 @@ struct srh_spmm_plan {
   int32_t* d_tickets = nullptr;    // one arrival counter per split row, self re-arming
   float* d_partial = nullptr;      // n_slots * 256 floats (enough for d <= 256)
 };
+
+// spmm_rows_kernel serves the whole-row widths; its task lists are the plan's index 1..3
+static bool is_rows_width(int32_t d) { return d == 64 || d == 128 || d == 256; }
+static int rows_gi(int32_t d) { return d == 64 ? 1 : d == 128 ? 2 : 3; }
+
+// room for max(1, v.size()) records on the device, filled with v
+template <class T>
+static hipError_t upload(T** dst, const std::vector<T>& v) {
+  hipError_t err = hipMalloc(dst, sizeof(T) * std::max<size_t>(1, v.size()));
+  if (err == hipSuccess && !v.empty()) err = hipMemcpy(*dst, v.data(), sizeof(T) * v.size(), hipMemcpyHostToDevice);
+  return err;
+}
 
 // host view of the epilogue (include/selfrec_hip.h) -> the kernels' argument block, with every check the ABI promises
 static srh_status_t translate_epilogue(const srh_spmm_epilogue_t* epi, int32_t d, const float* d_x, const float* d_y,
@@ -1430,6 +1362,98 @@ static srh_status_t translate_epilogue(const srh_spmm_epilogue_t* epi, int32_t d
   }
   SRH_REQUIRE(d > 32 || ep.noise_d_full % 32 == 0 || !(ep.flags & SRH_EPI_PERTURB),
               "spmm_f32: PERTURB on %d-wide rows needs the whole row width (a multiple of 32) in noise_d_full", d);
+  return SRH_OK;
+}
+
+// The flavours of spmm_rows_kernel: its bool template arguments by name (the comment above the kernel describes each)
+enum class Rows { Plain, ColMask, Probe, LatePf, Floor, Adam };
+
+// false: no kernel of this flavour is built for width d (nothing was launched)
+template <Rows F>
+static bool launch_rows(const srh_spmm_plan_t* plan, int32_t d, const int32_t* d_indices, const float* d_vals, const float* d_x,
+                        float* d_y, const DevEpilogue& ep, int n_fetch, const srh_batch_fetch_args_t& fetch_args,
+                        hipStream_t st) {
+  const int gi = rows_gi(d);
+#define SRH_LAUNCH_ROWS(LPR)                                                                                            \
+  spmm_rows_kernel<LPR, F == Rows::ColMask, F == Rows::Probe, F == Rows::LatePf, F == Rows::Floor, F == Rows::Adam>    \
+      <<<(plan->n_run[gi] + 3) / 4 + n_fetch, 256, 0, st>>>(                                                             \
+          plan->d_tasks64[gi], plan->n_run[gi], d_indices, d_vals, reinterpret_cast<const float4*>(d_x),                \
+          reinterpret_cast<float4*>(d_y), reinterpret_cast<float4*>(plan->d_partial), plan->d_heavy, plan->d_slot_owner, \
+          plan->d_tickets, ep, n_fetch, fetch_args)
+  switch (d) {
+    case 64: SRH_LAUNCH_ROWS(16); break;
+    // (late prefetch was measured, and is built, at d = 64 only)
+    case 128: if constexpr (F != Rows::LatePf) SRH_LAUNCH_ROWS(32); else return false; break;
+    case 256: if constexpr (F != Rows::LatePf) SRH_LAUNCH_ROWS(64); else return false; break;
+    default: return false;
+  }
+#undef SRH_LAUNCH_ROWS
+  return true;
+}
+
+// every product launch: srh_spmm_f32 / _with_fetch, the probe (d_stamps) and the gather bound (floor_only)
+static srh_status_t spmm_launch(const srh_spmm_plan_t* plan, const int32_t* d_indices, const float* d_vals, const float* d_x,
+                                float* d_y, int32_t d, const srh_spmm_epilogue_t* epi, const srh_batch_fetch_args_t* fetch,
+                                unsigned long long* d_stamps, void* stream, bool floor_only = false) {
+  srh_batch_fetch_args_t fetch_args{};
+  int n_fetch = 0;
+  if (fetch) {
+    SRH_REQUIRE(d >= 64 && !(epi && (epi->d_col_mark || epi->d_row_mark)),
+                "spmm_f32_with_fetch: d >= 64, and the product must not depend on the batch's marks");
+    if (srh_status_t rc = srh::check_fetch_args(fetch, fetch_args)) return rc;
+    n_fetch = srh::kFetchBlocks;
+  }
+  SRH_REQUIRE(plan && d_indices && d_x && d_y, "spmm_f32: null argument");
+  SRH_REQUIRE(d_vals || (d >= 64 && !(epi && epi->d_col_mark)),
+              "spmm_f32: a pattern matrix (d_vals == NULL) needs d >= 64 and no column marks");
+  SRH_REQUIRE(srh::dim_supported(d) || d == 8 || d == 16, "spmm_f32: d=%d unsupported (need 8, 16, 32, 64, 128 or 256)", d);
+  SRH_REQUIRE(d_x != d_y, "spmm_f32: x and y must not alias");
+  SRH_REQUIRE(plan->n_cols * (int64_t)d * 4 < (int64_t(1) << 32), "spmm_f32: x (%lld rows x %d) must be smaller than 4 GiB",
+              (long long)plan->n_cols, d);
+  DevEpilogue ep{};
+  if (srh_status_t rc = translate_epilogue(epi, d, d_x, d_y, ep)) return rc;
+  hipStream_t st = srh::as_stream(stream);
+  // one kernel per table width: a row-group of d/4 lanes per gathered x row (d >= 16), two lanes per row at d = 8
+#define SRH_LAUNCH(KERNEL, GI, XT, YT)                                                                              \
+  KERNEL<<<(plan->n_tasks[GI] + 3) / 4, 256, 0, st>>>(plan->d_tasks[GI], plan->n_tasks[GI], plan->d_tsegs, d_indices,  \
+                                                      d_vals, reinterpret_cast<const XT*>(d_x), reinterpret_cast<YT*>(d_y), \
+                                                      reinterpret_cast<YT*>(plan->d_partial), plan->d_heavy,          \
+                                                      plan->d_slot_owner, plan->d_tickets, ep)
+  switch (d) {
+    case 8: SRH_LAUNCH(spmm_pair_kernel, 0, float, float); break;
+    case 16: SRH_LAUNCH(spmm_slice_kernel<4>, 4, float4, float4); break;
+    case 32: SRH_LAUNCH(spmm_slice_kernel<8>, 0, float4, float4); break;
+    default: {
+      // (the gather offsets carry "no gather" in their sign bit: the table must stay below 2 GiB)
+      SRH_REQUIRE(plan->n_cols * (int64_t)d * 4 < (int64_t(1) << 31), "spmm_f32: x (%lld rows x %d) must be smaller than 2 GiB",
+                  (long long)plan->n_cols, d);
+      ep.stamps = d_stamps;
+      SRH_REQUIRE(!(ep.flags & SRH_EPI_ADAM) || !(floor_only || d_stamps || ep.col_mark),
+                  "spmm_f32: ADAM runs on the plain launch (no column marks, not under the probes)");
+      SRH_REQUIRE(floor_only || !d_stamps || !ep.col_mark, "spmm_f32_probe: no column marks");
+      const Rows flavour = floor_only                   ? Rows::Floor
+                           : d_stamps                   ? Rows::Probe
+                           : ep.col_mark                ? Rows::ColMask
+                           : (ep.flags & SRH_EPI_ADAM)  ? Rows::Adam
+                           : (ep.row_mark && d == 64)   ? Rows::LatePf     // row-masked launch: late prefetch
+                                                        : Rows::Plain;
+      bool launched = false;
+#define SRH_ROWS_CASE(F) \
+  case Rows::F: launched = launch_rows<Rows::F>(plan, d, d_indices, d_vals, d_x, d_y, ep, n_fetch, fetch_args, st); break
+      switch (flavour) {
+        SRH_ROWS_CASE(Floor);
+        SRH_ROWS_CASE(Probe);
+        SRH_ROWS_CASE(ColMask);
+        SRH_ROWS_CASE(Adam);
+        SRH_ROWS_CASE(LatePf);
+        SRH_ROWS_CASE(Plain);
+      }
+#undef SRH_ROWS_CASE
+      SRH_REQUIRE(launched, "spmm_f32: no kernel for this launch flavour at d=%d", d);
+    }
+  }
+#undef SRH_LAUNCH
+  SRH_LAUNCH_CHECK();
   return SRH_OK;
 }
 
@@ -1548,13 +1572,10 @@ srh_status_t srh_spmm_plan_create(srh_spmm_plan_t** out, int64_t n_rows, int64_t
     }
   }
   for (int k = 0; k < 16; ++k) tsegs.push_back({0, 0, 0, -1});       // padding records (see d_tsegs)
-  hipError_t err = hipMalloc(&p->d_tsegs, sizeof(Seg) * tsegs.size());
-  if (err == hipSuccess) err = hipMemcpy(p->d_tsegs, tsegs.data(), sizeof(Seg) * tsegs.size(), hipMemcpyHostToDevice);
+  hipError_t err = upload(&p->d_tsegs, tsegs);
   for (int gi = 0; gi < 5 && err == hipSuccess; ++gi) {
     p->n_tasks[gi] = (int32_t)tasks[gi].size();
-    err = hipMalloc(&p->d_tasks[gi], sizeof(Task) * std::max<size_t>(1, tasks[gi].size()));
-    if (err == hipSuccess && !tasks[gi].empty())
-      err = hipMemcpy(p->d_tasks[gi], tasks[gi].data(), sizeof(Task) * tasks[gi].size(), hipMemcpyHostToDevice);
+    err = upload(&p->d_tasks[gi], tasks[gi]);
   }
   // spmm_rows_kernel (d = 64 / 128 / 256) reads one self-contained 64-byte record per wave
   for (int gi = 1; gi <= 3 && err == hipSuccess; ++gi) {
@@ -1572,19 +1593,15 @@ srh_status_t srh_spmm_plan_create(srh_spmm_plan_t** out, int64_t n_rows, int64_t
       }
       t64[k] = r;
     }
-    err = hipMalloc(&p->d_tasks64[gi], sizeof(Task64) * std::max<size_t>(1, t64.size()));
-    if (err == hipSuccess && !t64.empty())
-      err = hipMemcpy(p->d_tasks64[gi], t64.data(), sizeof(Task64) * t64.size(), hipMemcpyHostToDevice);
+    err = upload(&p->d_tasks64[gi], t64);
     p->n_run[gi] = (int32_t)t64.size();
     p->cap64[gi] = std::max<size_t>(1, t64.size());
     p->h_tasks64[gi] = std::move(t64);
   }
   if (err == hipSuccess && !heavy.empty()) {
-    err = hipMalloc(&p->d_heavy, sizeof(Heavy) * heavy.size());
-    if (err == hipSuccess) err = hipMemcpy(p->d_heavy, heavy.data(), sizeof(Heavy) * heavy.size(), hipMemcpyHostToDevice);
+    err = upload(&p->d_heavy, heavy);
     if (err == hipSuccess) err = hipMalloc(&p->d_partial, sizeof(float) * 256 * (size_t)n_slots);
-    if (err == hipSuccess) err = hipMalloc(&p->d_slot_owner, sizeof(int32_t) * slot_owner.size());
-    if (err == hipSuccess) err = hipMemcpy(p->d_slot_owner, slot_owner.data(), sizeof(int32_t) * slot_owner.size(), hipMemcpyHostToDevice);
+    if (err == hipSuccess) err = upload(&p->d_slot_owner, slot_owner);
     if (err == hipSuccess) err = hipMalloc(&p->d_tickets, sizeof(int32_t) * heavy.size());
     if (err == hipSuccess) err = hipMemset(p->d_tickets, 0, sizeof(int32_t) * heavy.size());
   }
@@ -1599,13 +1616,12 @@ srh_status_t srh_spmm_plan_create(srh_spmm_plan_t** out, int64_t n_rows, int64_t
 
 void srh_spmm_plan_destroy(srh_spmm_plan_t* p) {
   if (!p) return;
-  if (p->d_heavy) (void)hipFree(p->d_heavy);
-  if (p->d_partial) (void)hipFree(p->d_partial);
-  if (p->d_slot_owner) (void)hipFree(p->d_slot_owner);
-  if (p->d_tickets) (void)hipFree(p->d_tickets);
-  if (p->d_tsegs) (void)hipFree(p->d_tsegs);
-  for (int gi = 0; gi < 5; ++gi) if (p->d_tasks[gi]) (void)hipFree(p->d_tasks[gi]);
-  for (int gi = 0; gi < 5; ++gi) if (p->d_tasks64[gi]) (void)hipFree(p->d_tasks64[gi]);
+  void* const single[] = {p->d_heavy, p->d_partial, p->d_slot_owner, p->d_tickets, p->d_tsegs};
+  for (void* q : single) if (q) (void)hipFree(q);
+  for (int gi = 0; gi < 5; ++gi) {
+    if (p->d_tasks[gi]) (void)hipFree(p->d_tasks[gi]);
+    if (p->d_tasks64[gi]) (void)hipFree(p->d_tasks64[gi]);
+  }
   delete p;
 }
 
@@ -1635,10 +1651,6 @@ srh_status_t srh_spmm_f32(const srh_spmm_plan_t* plan, const int32_t* d_indptr,
   return srh_spmm_f32_with_fetch(plan, d_indptr, d_indices, d_vals, d_x, d_y, d, epi, nullptr, stream);
 }
 
-static srh_status_t spmm_launch(const srh_spmm_plan_t* plan, const int32_t* d_indices, const float* d_vals, const float* d_x,
-                                float* d_y, int32_t d, const srh_spmm_epilogue_t* epi, const srh_batch_fetch_args_t* fetch,
-                                unsigned long long* d_stamps, void* stream, bool floor_only = false);
-
 srh_status_t srh_spmm_f32_with_fetch(const srh_spmm_plan_t* plan, const int32_t* d_indptr, const int32_t* d_indices,
                                      const float* d_vals, const float* d_x, float* d_y, int32_t d,
                                      const srh_spmm_epilogue_t* epi, const srh_batch_fetch_args_t* fetch, void* stream) {
@@ -1649,13 +1661,13 @@ srh_status_t srh_spmm_f32_with_fetch(const srh_spmm_plan_t* plan, const int32_t*
 srh_status_t srh_spmm_f32_probe(const srh_spmm_plan_t* plan, const int32_t* d_indices, const float* d_vals, const float* d_x,
                                 float* d_y, int32_t d, const srh_spmm_epilogue_t* epi, uint64_t* d_stamps, void* stream) {
   SRH_REQUIRE(d_stamps, "spmm_f32_probe: null stamp buffer");
-  SRH_REQUIRE(d == 64 || d == 128 || d == 256, "spmm_f32_probe: d=%d unsupported (64, 128 or 256)", d);
+  SRH_REQUIRE(is_rows_width(d), "spmm_f32_probe: d=%d unsupported (64, 128 or 256)", d);
   return spmm_launch(plan, d_indices, d_vals, d_x, d_y, d, epi, nullptr, reinterpret_cast<unsigned long long*>(d_stamps), stream);
 }
 
 srh_status_t srh_spmm_gather_bound(const srh_spmm_plan_t* plan, const int32_t* d_indices, const float* d_x, float* d_scratch,
                                    int32_t d, void* stream) {
-  SRH_REQUIRE(d == 64 || d == 128 || d == 256, "spmm_gather_bound: d=%d unsupported (64, 128 or 256)", d);
+  SRH_REQUIRE(is_rows_width(d), "spmm_gather_bound: d=%d unsupported (64, 128 or 256)", d);
   SRH_REQUIRE(d_scratch, "spmm_gather_bound: null scratch row");
   return spmm_launch(plan, d_indices, nullptr, d_x, d_scratch, d, nullptr, nullptr, nullptr, stream, true);
 }
@@ -1663,7 +1675,7 @@ srh_status_t srh_spmm_gather_bound(const srh_spmm_plan_t* plan, const int32_t* d
 srh_status_t srh_gather_floor_probe(const int32_t* d_indices, int64_t n_idx, const float* d_x, int64_t n_x_rows, int32_t d,
                                     int32_t blocks, float* d_sink, void* stream) {
   SRH_REQUIRE(d_indices && d_x && d_sink && n_idx > 0 && n_x_rows > 0, "gather_floor_probe: null / empty argument");
-  SRH_REQUIRE(d == 64 || d == 128 || d == 256, "gather_floor_probe: d=%d unsupported (64, 128 or 256)", d);
+  SRH_REQUIRE(is_rows_width(d), "gather_floor_probe: d=%d unsupported (64, 128 or 256)", d);
   SRH_REQUIRE(n_x_rows * (int64_t)d * 4 < (int64_t(1) << 32), "gather_floor_probe: x must be smaller than 4 GiB");
   SRH_REQUIRE(blocks > 0 && blocks <= (1 << 20), "gather_floor_probe: bad grid");
   hipStream_t st = srh::as_stream(stream);
@@ -1678,13 +1690,13 @@ srh_status_t srh_gather_floor_probe(const int32_t* d_indices, int64_t n_idx, con
 
 int32_t srh_spmm_plan_run_tasks(const srh_spmm_plan_t* plan, int32_t d) {
   if (!plan) return -1;
-  return d == 64 ? plan->n_run[1] : d == 128 ? plan->n_run[2] : d == 256 ? plan->n_run[3] : -1;
+  return is_rows_width(d) ? plan->n_run[rows_gi(d)] : -1;
 }
 
 srh_status_t srh_spmm_plan_set_xcd_shares(srh_spmm_plan_t* plan, int32_t d, const int32_t* h_blocks_per_xcd) {
   SRH_REQUIRE(plan, "spmm_plan_set_xcd_shares: null plan");
-  SRH_REQUIRE(d == 64 || d == 128 || d == 256, "spmm_plan_set_xcd_shares: d=%d unsupported (64, 128 or 256)", d);
-  const int gi = d == 64 ? 1 : d == 128 ? 2 : 3;
+  SRH_REQUIRE(is_rows_width(d), "spmm_plan_set_xcd_shares: d=%d unsupported (64, 128 or 256)", d);
+  const int gi = rows_gi(d);
   const std::vector<Task64>& canon = plan->h_tasks64[gi];
   const size_t nb = (canon.size() + 3) / 4;                 // canonical blocks (4 records each)
   Task64 empty{};
@@ -1730,81 +1742,6 @@ srh_status_t srh_spmm_plan_set_xcd_shares(srh_spmm_plan_t* plan, int32_t d, cons
     err = hipMemcpy(plan->d_tasks64[gi], list.data(), sizeof(Task64) * list.size(), hipMemcpyHostToDevice);
   if (err != hipSuccess) { srh::set_error("spmm_plan_set_xcd_shares: %s", hipGetErrorString(err)); return SRH_ERR_HIP; }
   plan->n_run[gi] = (int32_t)list.size();
-  return SRH_OK;
-}
-
-static srh_status_t spmm_launch(const srh_spmm_plan_t* plan, const int32_t* d_indices, const float* d_vals, const float* d_x,
-                                float* d_y, int32_t d, const srh_spmm_epilogue_t* epi, const srh_batch_fetch_args_t* fetch,
-                                unsigned long long* d_stamps, void* stream, bool floor_only) {
-  srh_batch_fetch_args_t fetch_args{};
-  int n_fetch = 0;
-  if (fetch) {
-    SRH_REQUIRE(d >= 64 && !(epi && (epi->d_col_mark || epi->d_row_mark)),
-                "spmm_f32_with_fetch: d >= 64, and the product must not depend on the batch's marks");
-    if (srh_status_t rc = srh::check_fetch_args(fetch, fetch_args)) return rc;
-    n_fetch = srh::kFetchBlocks;
-  }
-  SRH_REQUIRE(plan && d_indices && d_x && d_y, "spmm_f32: null argument");
-  SRH_REQUIRE(d_vals || (d >= 64 && !(epi && epi->d_col_mark)),
-              "spmm_f32: a pattern matrix (d_vals == NULL) needs d >= 64 and no column marks");
-  SRH_REQUIRE(srh::dim_supported(d) || d == 8 || d == 16, "spmm_f32: d=%d unsupported (need 8, 16, 32, 64, 128 or 256)", d);
-  SRH_REQUIRE(d_x != d_y, "spmm_f32: x and y must not alias");
-  SRH_REQUIRE(plan->n_cols * (int64_t)d * 4 < (int64_t(1) << 32), "spmm_f32: x (%lld rows x %d) must be smaller than 4 GiB",
-              (long long)plan->n_cols, d);
-  DevEpilogue ep{};
-  if (srh_status_t rc = translate_epilogue(epi, d, d_x, d_y, ep)) return rc;
-  hipStream_t st = srh::as_stream(stream);
-  // one kernel per table width: a row-group of d/4 lanes per gathered x row (d >= 16), two lanes per row at d = 8
-#define SRH_LAUNCH(KERNEL, GI, XT, YT)                                                                              \
-  KERNEL<<<(plan->n_tasks[GI] + 3) / 4, 256, 0, st>>>(plan->d_tasks[GI], plan->n_tasks[GI], plan->d_tsegs, d_indices,  \
-                                                      d_vals, reinterpret_cast<const XT*>(d_x), reinterpret_cast<YT*>(d_y), \
-                                                      reinterpret_cast<YT*>(plan->d_partial), plan->d_heavy,          \
-                                                      plan->d_slot_owner, plan->d_tickets, ep)
-  switch (d) {
-    case 8: SRH_LAUNCH(spmm_pair_kernel, 0, float, float); break;
-    case 16: SRH_LAUNCH(spmm_slice_kernel<4>, 4, float4, float4); break;
-    case 32: SRH_LAUNCH(spmm_slice_kernel<8>, 0, float4, float4); break;
-    default: {
-      // (the gather offsets carry "no gather" in their sign bit: the table must stay below 2 GiB)
-      SRH_REQUIRE(plan->n_cols * (int64_t)d * 4 < (int64_t(1) << 31), "spmm_f32: x (%lld rows x %d) must be smaller than 2 GiB",
-                  (long long)plan->n_cols, d);
-#define SRH_LAUNCH_ROWS(LPRV, GI, CM, PR, ...)                                                                       \
-  spmm_rows_kernel<LPRV, CM, PR, ##__VA_ARGS__><<<(plan->n_run[GI] + 3) / 4 + n_fetch, 256, 0, st>>>(           \
-      plan->d_tasks64[GI], plan->n_run[GI], d_indices, d_vals, reinterpret_cast<const float4*>(d_x),                \
-      reinterpret_cast<float4*>(d_y), reinterpret_cast<float4*>(plan->d_partial), plan->d_heavy, plan->d_slot_owner, \
-      plan->d_tickets, ep, n_fetch, fetch_args)
-      ep.stamps = d_stamps;
-      SRH_REQUIRE(!(ep.flags & SRH_EPI_ADAM) || !(floor_only || d_stamps || ep.col_mark),
-                  "spmm_f32: ADAM runs on the plain launch (no column marks, not under the probes)");
-      if (floor_only) {
-        if (d == 64) SRH_LAUNCH_ROWS(16, 1, false, false, false, true);
-        else if (d == 128) SRH_LAUNCH_ROWS(32, 2, false, false, false, true);
-        else SRH_LAUNCH_ROWS(64, 3, false, false, false, true);
-      } else if (d_stamps) {
-        SRH_REQUIRE(!ep.col_mark, "spmm_f32_probe: no column marks");
-        if (d == 64) SRH_LAUNCH_ROWS(16, 1, false, true);
-        else if (d == 128) SRH_LAUNCH_ROWS(32, 2, false, true);
-        else SRH_LAUNCH_ROWS(64, 3, false, true);
-      } else if (ep.col_mark) {
-        if (d == 64) SRH_LAUNCH_ROWS(16, 1, true, false);
-        else if (d == 128) SRH_LAUNCH_ROWS(32, 2, true, false);
-        else SRH_LAUNCH_ROWS(64, 3, true, false);
-      } else if (ep.flags & SRH_EPI_ADAM) {
-        if (d == 64) SRH_LAUNCH_ROWS(16, 1, false, false, false, false, true);
-        else if (d == 128) SRH_LAUNCH_ROWS(32, 2, false, false, false, false, true);
-        else SRH_LAUNCH_ROWS(64, 3, false, false, false, false, true);
-      } else if (ep.row_mark && d == 64) {
-        SRH_LAUNCH_ROWS(16, 1, false, false, true);              // row-masked launch: late prefetch (measured at d = 64)
-      } else {
-        if (d == 64) SRH_LAUNCH_ROWS(16, 1, false, false);
-        else if (d == 128) SRH_LAUNCH_ROWS(32, 2, false, false);
-        else SRH_LAUNCH_ROWS(64, 3, false, false);
-      }
-#undef SRH_LAUNCH_ROWS
-    }
-  }
-#undef SRH_LAUNCH
-  SRH_LAUNCH_CHECK();
   return SRH_OK;
 }
 

@@ -190,27 +190,16 @@ __device__ __forceinline__ void gather8_novals(unsigned cs, unsigned sub16, cons
 
 __device__ __forceinline__ float4 to_f4(const Acc& a) { return make_float4(a.lo.x, a.lo.y, a.hi.x, a.hi.y); }
 
-// in-kernel finish of a split row (same protocol as spmm_rows_kernel)
+// in-kernel finish of a split row: the product's hand-off (SRH_SPLIT_ARRIVE, csrc/spmm.hip)
 __device__ __forceinline__ void finish_split(float4 acc, int row, int slot, int lane, int g, int sub, float4* __restrict__ Y,
                                              float4* __restrict__ partial, const Heavy* __restrict__ heavy,
                                              const int32_t* __restrict__ slot_owner, int32_t* __restrict__ tickets,
                                              const DevEpilogue& ep) {
   constexpr int LPR = 16, G = 4;
   if (g == 0) store_f4_sc1(partial + (size_t)slot * LPR + sub, acc);
-  const int hid = __builtin_amdgcn_readfirstlane(slot_owner[slot]);
-  const Heavy h = heavy[hid];
-  const int hfirst = __builtin_amdgcn_readfirstlane(h.first_slot);
-  const int hn = __builtin_amdgcn_readfirstlane(h.n_slots);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  int ticket = 0;
-  if (lane == 0) ticket = __hip_atomic_fetch_add(tickets + hid, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  ticket = __builtin_amdgcn_readfirstlane(ticket);
-  if (ticket != hn - 1) return;
-  if (lane == 0) __hip_atomic_store(tickets + hid, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  float4 sum = f4_zero();
-  sum = sum_partials_agent(partial + (size_t)hfirst * LPR + sub, g, G, hn, LPR);
-#pragma unroll
-  for (int m = LPR; m < 64; m <<= 1) sum = f4_add(sum, f4_shfl_xor(sum, m));
+  SRH_SPLIT_ARRIVE(slot, lane, heavy, slot_owner, tickets, first, n, return);
+  float4 sum = sum_partials_agent(partial + (size_t)first * LPR + sub, g, G, n, LPR);
+  SRH_GROUPS_SUM(LPR, sum);
   row_epilogue<LPR>(sum, row, sub, g == 0, Y, ep);
 }
 
@@ -321,8 +310,7 @@ __global__ __launch_bounds__(256) void rows_kernel(const Task* __restrict__ task
       else if (base + CH < e) fetch(base + CH + 16 * g + e16, e, cs, v);
     }
     float4 a4 = to_f4(acc);
-#pragma unroll
-    for (int m = LPR; m < 64; m <<= 1) a4 = f4_add(a4, f4_shfl_xor(a4, m));
+    SRH_GROUPS_SUM(LPR, a4);
     if (slot < 0) { row_epilogue<LPR>(a4, row, sub, g == 0, Y, ep); stamp_end(0); return; }
     finish_split(a4, row, slot, lane, g, sub, Y, partial, heavy, slot_owner, tickets, ep);
     stamp_end(1);
@@ -334,8 +322,7 @@ __global__ __launch_bounds__(256) void rows_kernel(const Task* __restrict__ task
   const bool live = have && (!ep.row_mark || ep.row_mark[row] == stamp);
   if (!live) e = s;
   int maxlen = e - s;
-#pragma unroll
-  for (int m = LPR; m < 64; m <<= 1) maxlen = max(maxlen, __shfl_xor(maxlen, m));
+  SRH_GROUPS_MAX(LPR, maxlen);
   maxlen = __builtin_amdgcn_readfirstlane(maxlen);
   unsigned cs, csn = 0;
   float v, vn = 0.f;
@@ -413,8 +400,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DEPTH == 2 
         maxlen = max(max(e0 - s0, e1 - s1), max(e2 - s2, e3 - s3));          // scalar unit: the record is in SGPRs
       } else {
         maxlen = e - s;
-#pragma unroll
-        for (int m = LPR; m < 64; m <<= 1) maxlen = max(maxlen, __shfl_xor(maxlen, m));
+        SRH_GROUPS_MAX(LPR, maxlen);
         maxlen = __builtin_amdgcn_readfirstlane(maxlen);
       }
       w.rem0 = maxlen;
@@ -485,8 +471,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DEPTH == 2 
       if (cur.live) {
         const int row = __builtin_amdgcn_readfirstlane(cur.row), slot = __builtin_amdgcn_readfirstlane(cur.slot);
         float4 a4 = to_f4(acc);
-#pragma unroll
-        for (int m = LPR; m < 64; m <<= 1) a4 = f4_add(a4, f4_shfl_xor(a4, m));
+        SRH_GROUPS_SUM(LPR, a4);
         if (slot < 0) {
           if (LIGHT) light_epilogue(a4, row, sub, g == 0, Y, ep); else row_epilogue<LPR>(a4, row, sub, g == 0, Y, ep);
         } else {
@@ -608,8 +593,7 @@ __global__ __launch_bounds__(256) void rows_kernel3(const Task64* __restrict__ t
     live = g < count && (!ep.row_mark || ep.row_mark[row] == stamp);
     if (!live) e = s;
     int maxlen = e - s;
-#pragma unroll
-    for (int m = LPR; m < 64; m <<= 1) maxlen = max(maxlen, __shfl_xor(maxlen, m));
+    SRH_GROUPS_MAX(LPR, maxlen);
     total = __builtin_amdgcn_readfirstlane(maxlen);
     j0 = s + e16; stride = 16;
   }
@@ -632,8 +616,7 @@ __global__ __launch_bounds__(256) void rows_kernel3(const Task64* __restrict__ t
   }
   if (kind == 0) {
     float4 a4 = to_f4(acc);
-#pragma unroll
-    for (int m = LPR; m < 64; m <<= 1) a4 = f4_add(a4, f4_shfl_xor(a4, m));
+    SRH_GROUPS_SUM(LPR, a4);
     if (slot < 0) { row_epilogue<LPR>(a4, row, sub, g == 0, Y, ep); return; }
     finish_split(a4, row, slot, lane, g, sub, Y, partial, heavy, slot_owner, tickets, ep);
     return;
@@ -687,8 +670,7 @@ void rows_kernel5(const Task64* __restrict__ tasks64, int n_coop_pad, int n_task
       cs = csn; v = vn;
     }
     float4 a4 = to_f4(acc);
-#pragma unroll
-    for (int m = LPR; m < 64; m <<= 1) a4 = f4_add(a4, f4_shfl_xor(a4, m));
+    SRH_GROUPS_SUM(LPR, a4);
     if (slot < 0) row_epilogue<LPR>(a4, row, sub, g == 0, Y, ep);
     else finish_split(a4, row, slot, lane, g, sub, Y, partial, heavy, slot_owner, tickets, ep);
   }
@@ -712,8 +694,7 @@ void rows_kernel5(const Task64* __restrict__ tasks64, int n_coop_pad, int n_task
     const bool live = e > s && (!ep.row_mark || ep.row_mark[row] == stamp);
     if (!live) { e = s; cs = 0x80000000u; }
     int maxlen = e - s;
-#pragma unroll
-    for (int m = LPR; m < 64; m <<= 1) maxlen = max(maxlen, __shfl_xor(maxlen, m));
+    SRH_GROUPS_MAX(LPR, maxlen);
     maxlen = __builtin_amdgcn_readfirstlane(maxlen);
     const int tn = t + W;
     int nrow = 0, ns = 0, ne = 0;
