@@ -850,6 +850,42 @@ srh_status_t srh_batch_softmax_fwd_bwd(const float* d_u, const float* d_v, int64
                                        double* d_loss, float* d_gu, float* d_gv, void* d_ws, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * (a-16) SASRec -- replaces the attention core of nn.MultiheadAttention as model/sequential/SASRec.py:107 calls it
+ * (causal attn_mask, dropout on the probabilities) and calculate_loss (SASRec.py:44-53).
+ *
+ * srh_seq_attn_fwd_f32: d_q, d_k, d_v, d_out are (B, L, H * dh) row-major, head h in columns [h dh, (h + 1) dh):
+ *   out[b, i, h] = sum_{j <= i} P~[b, h, i, j] v[b, j, h],  P = softmax_j(q_i . k_j / sqrt(dh)) over j <= i,
+ *   P~ = P * (keep ? 1 / (1 - drop_p) : 0).  keep[b][h][i][j] is d_keep[((b H + h) L + i) L + j] != 0 when d_keep is
+ *   given; else, when drop_p > 0, it is drawn from the counter RNG of the SpMM epilogue (tests/counter_rng.py): the word
+ *   j % 4 of float4 j / 4 at counter rng_counter + (b H + h) L + i, keep = u01(word) >= drop_p -- a pure function of
+ *   (seed, counter, b, h, row, col).  One call uses the counters [rng_counter, rng_counter + B H L): the caller advances
+ *   its counter by B * H * L per call.  d_lse (B, H, L) receives the rows' log-sum-exp; the B x L x L scores are never
+ *   written.
+ * srh_seq_attn_bwd_f32: from q, k, v, the forward's d_lse, the same dropout arguments and the upstream d_go: d_gq, d_gk,
+ *   d_gv (written).  dV = P~^T dO, dP = dO V^T, dS = P (m dP - rowsum(m dP P)), dQ = dS K / sqrt(dh),
+ *   dK = dS^T Q / sqrt(dh).
+ *   Envelope: 1 <= L <= 64, dh 32 or 64, H dh <= 128, any B >= 1; outside it SRH_ERR_UNSUPPORTED with a message.  One
+ *   workgroup produces every element in a fixed order: no float atomics, the same bits on every call.
+ * srh_seq_bce_fwd_bwd: for the rows r of d_hidden (R x d) with d_valid[r] != 0: x+ = h_r . table[pos[r]],
+ *   x- = h_r . table[neg[r]]; d_loss2[0] = mean BCEWithLogits(x+, 1), d_loss2[1] = mean BCEWithLogits(x-, 0) over the
+ *   n_valid valid rows (the caller's count of d_valid; the stable form max(x, 0) - x y + log1p(exp(-|x|)) in double,
+ *   summed in a fixed order).  d_gh (R x d): d(loss2[0] + loss2[1]) / dh; d_grows (2R x d): row r the gradient the row
+ *   contributes to table[pos[r]], row R + r to table[neg[r]] (zero rows where invalid) -- srh_rows_segment_sum_f32 over
+ *   [pos; neg] makes the table gradient.  d_ws >= srh_seq_bce_ws_bytes(R).
+ * ---------------------------------------------------------------------------------- */
+srh_status_t srh_seq_attn_fwd_f32(const float* d_q, const float* d_k, const float* d_v, int64_t B, int32_t L, int32_t H,
+                                  int32_t dh, const uint8_t* d_keep, uint64_t rng_seed, uint64_t rng_counter, float drop_p,
+                                  float* d_out, float* d_lse, void* stream);
+srh_status_t srh_seq_attn_bwd_f32(const float* d_q, const float* d_k, const float* d_v, const float* d_go,
+                                  const float* d_lse, int64_t B, int32_t L, int32_t H, int32_t dh, const uint8_t* d_keep,
+                                  uint64_t rng_seed, uint64_t rng_counter, float drop_p, float* d_gq, float* d_gk,
+                                  float* d_gv, void* stream);
+int64_t srh_seq_bce_ws_bytes(int64_t R);
+srh_status_t srh_seq_bce_fwd_bwd(const float* d_hidden, int64_t R, int32_t d, const float* d_table, int64_t n_table,
+                                 const int32_t* d_pos, const int32_t* d_neg, const uint8_t* d_valid, int64_t n_valid,
+                                 double* d_loss2, float* d_gh, float* d_grows, void* d_ws, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * (f-1) Dataset files -> id arrays -- replaces the python loops of data/loader.py:22-33
  * (FileIO.load_data_set: one "user item weight" line per interaction, single-space separated)
  * and data/ui_graph.py:29-45 (ids in first-appearance order of the training file; test pairs kept

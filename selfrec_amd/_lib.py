@@ -179,6 +179,11 @@ SIGNATURES = {
     "srh_rows_segment_sum_f32": (_i32, [_vp, _i64, _i32, _vp, _vp, _vp, _i64, _i64, _vp, _vp]),
     "srh_batch_softmax_ws_bytes": (_i64, [_i64, _i32]),
     "srh_batch_softmax_fwd_bwd": (_i32, [_vp, _vp, _i64, _i32, _f32, _vp, _vp, _vp, _vp, _vp]),
+    "srh_seq_attn_fwd_f32": (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _u64, _u64, _f32, _vp, _vp, _vp]),
+    "srh_seq_attn_bwd_f32": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _u64, _u64, _f32, _vp, _vp, _vp,
+                                    _vp]),
+    "srh_seq_bce_ws_bytes": (_i64, [_i64]),
+    "srh_seq_bce_fwd_bwd": (_i32, [_vp, _i64, _i32, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
     "srh_adam_step": (_i32, [_vp, _vp, _vp, _vp, _i64, _i64, _vp, _f32, _f32, _f32, _f32, _vp]),
     "srh_adam_step_reset": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _vp, _f32, _f32, _f32, _f32, _vp, _i32, _vp, _vp, _vp]),
     "srh_score_mask_topk": (_i32, [_vp, _vp, _i64, _vp, _i64, _i32, _vp, _vp, _i32, _vp, _i64, _vp, _vp, _vp]),

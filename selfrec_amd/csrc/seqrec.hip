@@ -1,0 +1,456 @@
+// SASRec (reference model/sequential/SASRec.py): causal self-attention over short sequences and the BCE loss.
+// DESIGN.md 4.9.
+//
+// Attention.  Q, K, V are the projected (B, L, H dh) row-major tensors, L <= 64, dh 32 or 64, H dh <= 128.  One workgroup
+// owns one (sequence, head); wave w owns the query rows 16w .. 16w + 15 and walks the key tiles t <= w (the tiles above
+// the diagonal are masked whole and never computed).
+//   srh_seq_attn_fwd_f32  K and V tiles sit in LDS.  S^T = K (Q / sqrt(dh))^T comes out of v_mfma_f32_16x16x4_f32 with
+//                         acc[t][reg] = S[query j16][key 16t + 4g + reg]; the causal mask, the row softmax (two
+//                         cross-lane steps over the four lanes that share a row) and the dropout multiplier are applied
+//                         on the accumulator, which is then the B operand of O^T += V^T P^T with the k order 4g + reg
+//                         matched by the A operand's row (the GEMM -> GEMM seam of ssl4rec.hip).  Only O and the row
+//                         log-sum-exp are written.
+//   srh_seq_attn_bwd_f32  the same ownership.  Pass 1 recomputes S and P = exp(S - lse), forms dP~ = dO V^T on the MFMA,
+//                         dS = P (m dP~ - rowsum(m dP~ P)) / sqrt(dh) on the accumulator and dQ = dS K through the seam.
+//                         Pass 2 turns the ownership to key tiles: P~ (then dS) of the whole (sequence, head) goes through
+//                         one LDS buffer, dO (then Q) replaces V (then K) in theirs, and wave w sums dV = P~^T dO and
+//                         dK = dS^T Q of the keys 16w .. 16w + 15 over the query tiles w .. in ascending order.
+// Every output element has one producer and one summation order: no atomics, no scratch, the same bits on every call.
+//
+// Dropout on P: keep[b][h][row][col] injected as bytes, or drawn from the counter RNG of common.h at counter
+// rng_counter + (b H + h) L + row, float4 number col / 4, word col % 4 (keep = u01(word) >= p); the backward redraws it.
+//
+// srh_seq_bce_fwd_bwd: one wave per hidden row gathers the target and the negative item rows, forms both logits and
+// writes the row's two loss terms (float64), dL/dh and the two per-row table gradients; one workgroup then sums the
+// terms in a fixed order.  The table gradient itself is srh_rows_segment_sum_f32 over the per-row gradients.
+#include "common.h"
+
+namespace {
+
+using namespace srh;
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+constexpr int kMaxL = 64;        // query / key rows a workgroup holds
+constexpr int kLdX = kMaxL + 8;  // LDS row stride (floats) of the P~ / dS buffer of the backward's second pass
+
+#define SRH_SUPPORTED(cond, ...)         \
+  do {                                   \
+    if (!(cond)) {                       \
+      ::srh::set_error(__VA_ARGS__);     \
+      return SRH_ERR_UNSUPPORTED;        \
+    }                                    \
+  } while (0)
+
+enum { DROP_NONE = 0, DROP_GIVEN = 1, DROP_DRAWN = 2 };
+
+struct AttnArgs {
+  const float *q, *k, *v;
+  const float *go, *lse_in;       // backward only
+  float *out, *lse;               // forward only
+  float *gq, *gk, *gv;            // backward only
+  const uint8_t* keep;
+  int L, H;
+  int drop;
+  uint32_t seed_lo, seed_hi;
+  uint64_t ctr;
+  float drop_p, drop_scale, qscale;
+};
+
+// rows [0, L) of one head's (L x DH) slice (row stride E floats) -> dst[r][c] with row stride DH + 4; rows >= L zero
+template <int DH>
+__device__ __forceinline__ void stage_tile(float* dst, const float* src, const int L, const int E) {
+  constexpr int LD = DH + 4;
+  for (int e = threadIdx.x; e < kMaxL * (DH / 4); e += 256) {
+    const int r = e / (DH / 4), v = e % (DH / 4);
+    const float4 x = r < L ? *reinterpret_cast<const float4*>(src + (int64_t)r * E + 4 * v) : f4_zero();
+    *reinterpret_cast<float4*>(&dst[r * LD + 4 * v]) = x;
+  }
+}
+
+// the dropout multiplier of P[row][16t + 4g + reg], reg = 0..3 (row < L)
+__device__ __forceinline__ void drop_mult4(const AttnArgs& a, const int64_t bh, const int row, const int t, const int g,
+                                           float m[4]) {
+  if (a.drop == DROP_NONE) {
+    m[0] = m[1] = m[2] = m[3] = 1.f;
+  } else if (a.drop == DROP_GIVEN) {
+    const int c0 = 16 * t + 4 * g;
+    const uint8_t* kp = a.keep + (bh * a.L + row) * a.L + c0;
+#pragma unroll
+    for (int reg = 0; reg < 4; ++reg) m[reg] = (c0 + reg < a.L && kp[reg] != 0) ? a.drop_scale : 0.f;
+  } else {
+    const uint4 w = counter_rng4(a.ctr + (uint64_t)(bh * a.L + row), (uint32_t)(4 * t + g), a.seed_lo, a.seed_hi);
+    m[0] = u01(w.x) >= a.drop_p ? a.drop_scale : 0.f;
+    m[1] = u01(w.y) >= a.drop_p ? a.drop_scale : 0.f;
+    m[2] = u01(w.z) >= a.drop_p ? a.drop_scale : 0.f;
+    m[3] = u01(w.w) >= a.drop_p ? a.drop_scale : 0.f;
+  }
+}
+
+// sum / max over the four lanes (g = 0..3) that share query row j16: the same bits in all four
+__device__ __forceinline__ float row_sum4(float v) {
+  v += __shfl_xor(v, 16);
+  v += __shfl_xor(v, 32);
+  return v;
+}
+__device__ __forceinline__ float row_max4(float v) {
+  v = fmaxf(v, __shfl_xor(v, 16));
+  v = fmaxf(v, __shfl_xor(v, 32));
+  return v;
+}
+
+// st[t][reg] = S[query 16 wave + j16][key 16t + 4g + reg] for the tiles t <= wave; qf: the lane's scaled query operand
+template <int DH>
+__device__ __forceinline__ void scores(const float* Ks, const float (&qf)[DH / 4], const int wave, const int g,
+                                       const int j16, f32x4 (&st)[4]) {
+  constexpr int LD = DH + 4;
+#pragma unroll
+  for (int t = 0; t < 4; ++t) {
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    if (t <= wave) {
+      const float* arow = &Ks[(16 * t + j16) * LD + g];
+#pragma unroll
+      for (int k = 0; k < DH / 4; ++k) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(arow[4 * k], qf[k], acc, 0, 0, 0);
+    }
+    st[t] = acc;
+  }
+}
+
+// out[u][reg] = sum over the keys of tiles t <= wave of Xs[key][16u + 4g + reg] bt[key], for query j16: the
+// accumulator-shaped bt[t][reg] (key 16t + 4g + reg) is the B operand as it stands, Xs (keys x DH in LDS) gives the A
+// operand's row for that k order
+template <int DH>
+__device__ __forceinline__ void seam_product(const float* Xs, const f32x4 (&bt)[4], const int wave, const int g,
+                                             const int j16, f32x4 (&out)[DH / 16]) {
+  constexpr int LD = DH + 4;
+#pragma unroll
+  for (int u = 0; u < DH / 16; ++u) out[u] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int t = 0; t < 4; ++t) {
+    if (t <= wave) {
+#pragma unroll
+      for (int reg = 0; reg < 4; ++reg) {
+        const float* arow = &Xs[(16 * t + 4 * g + reg) * LD + j16];
+#pragma unroll
+        for (int u = 0; u < DH / 16; ++u)
+          out[u] = __builtin_amdgcn_mfma_f32_16x16x4f32(arow[16 * u], bt[t][reg], out[u], 0, 0, 0);
+      }
+    }
+  }
+}
+
+// ---- forward -----------------------------------------------------------------------------------------------------------
+template <int DH>
+__global__ __launch_bounds__(256) void attn_fwd(AttnArgs a) {
+  constexpr int LD = DH + 4;
+  __shared__ float Ks[kMaxL * LD];
+  __shared__ float Vs[kMaxL * LD];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, g = lane >> 4, j16 = lane & 15;
+  const int64_t bh = blockIdx.x;
+  const int64_t b = bh / a.H;
+  const int h = (int)(bh % a.H), L = a.L, E = a.H * DH;
+  const int64_t base = b * L * E + h * DH;
+  stage_tile<DH>(Ks, a.k + base, L, E);
+  stage_tile<DH>(Vs, a.v + base, L, E);
+  __syncthreads();
+  if (16 * wave >= L) return;
+  const int row = 16 * wave + j16;
+  const bool rok = row < L;
+
+  float qf[DH / 4];
+#pragma unroll
+  for (int k = 0; k < DH / 4; ++k) qf[k] = rok ? a.q[base + (int64_t)row * E + 4 * k + g] * a.qscale : 0.f;
+  f32x4 st[4];
+  scores<DH>(Ks, qf, wave, g, j16, st);
+
+  // causal mask and softmax of the row (key 0 <= row always: no empty row)
+  float mx = -INFINITY;
+#pragma unroll
+  for (int t = 0; t < 4; ++t)
+#pragma unroll
+    for (int reg = 0; reg < 4; ++reg)
+      if (16 * t + 4 * g + reg <= row) mx = fmaxf(mx, st[t][reg]);
+  mx = row_max4(mx);
+  float sum = 0.f;
+#pragma unroll
+  for (int t = 0; t < 4; ++t)
+#pragma unroll
+    for (int reg = 0; reg < 4; ++reg) {
+      const float p = (16 * t + 4 * g + reg <= row) ? expf(st[t][reg] - mx) : 0.f;
+      st[t][reg] = p;
+      sum += p;
+    }
+  sum = row_sum4(sum);
+  const float inv = 1.f / sum;
+#pragma unroll
+  for (int t = 0; t < 4; ++t) {
+    float m[4] = {1.f, 1.f, 1.f, 1.f};
+    if (rok && t <= wave) drop_mult4(a, bh, row, t, g, m);
+#pragma unroll
+    for (int reg = 0; reg < 4; ++reg) st[t][reg] = rok ? st[t][reg] * inv * m[reg] : 0.f;
+  }
+
+  f32x4 ot[DH / 16];
+  seam_product<DH>(Vs, st, wave, g, j16, ot);
+  if (!rok) return;
+#pragma unroll
+  for (int u = 0; u < DH / 16; ++u)
+    *reinterpret_cast<float4*>(a.out + base + (int64_t)row * E + 16 * u + 4 * g) =
+        make_float4(ot[u][0], ot[u][1], ot[u][2], ot[u][3]);
+  if (g == 0) a.lse[bh * L + row] = mx + logf(sum);
+}
+
+// ---- backward ----------------------------------------------------------------------------------------------------------
+// dX[key 16 wave + j16][dim] = sum over queries of Xs[query][key] Ys[query][dim], query tiles wave .. nT - 1 ascending
+template <int DH>
+__device__ __forceinline__ void key_tile_product(const float* Xs, const float* Ys, const int wave, const int nT, const int g,
+                                                 const int j16, f32x4 (&out)[DH / 16]) {
+  constexpr int LD = DH + 4;
+#pragma unroll
+  for (int u = 0; u < DH / 16; ++u) out[u] = f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int tq = wave; tq < nT; ++tq) {
+#pragma unroll
+    for (int kk = 0; kk < 4; ++kk) {
+      const int qr = 16 * tq + 4 * kk + g;
+      const float bv = Xs[qr * kLdX + 16 * wave + j16];
+      const float* arow = &Ys[qr * LD + j16];
+#pragma unroll
+      for (int u = 0; u < DH / 16; ++u) out[u] = __builtin_amdgcn_mfma_f32_16x16x4f32(arow[16 * u], bv, out[u], 0, 0, 0);
+    }
+  }
+}
+
+template <int DH>
+__global__ __launch_bounds__(256) void attn_bwd(AttnArgs a) {
+  constexpr int LD = DH + 4;
+  __shared__ float Ks[kMaxL * LD];     // K, then Q
+  __shared__ float Vs[kMaxL * LD];     // V, then dO
+  __shared__ float Xs[kMaxL * kLdX];   // P~, then dS
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, g = lane >> 4, j16 = lane & 15;
+  const int64_t bh = blockIdx.x;
+  const int64_t b = bh / a.H;
+  const int h = (int)(bh % a.H), L = a.L, E = a.H * DH;
+  const int64_t base = b * L * E + h * DH;
+  const int nT = (L + 15) / 16;
+  const bool active = wave < nT;
+  const int row = 16 * wave + j16;
+  const bool rok = active && row < L;
+  stage_tile<DH>(Ks, a.k + base, L, E);
+  stage_tile<DH>(Vs, a.v + base, L, E);
+  __syncthreads();
+
+  f32x4 pt[4], ds[4];
+#pragma unroll
+  for (int t = 0; t < 4; ++t) pt[t] = ds[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+  if (active) {
+    float qf[DH / 4], gof[DH / 4];
+#pragma unroll
+    for (int k = 0; k < DH / 4; ++k) {
+      qf[k] = rok ? a.q[base + (int64_t)row * E + 4 * k + g] * a.qscale : 0.f;
+      gof[k] = rok ? a.go[base + (int64_t)row * E + 4 * k + g] : 0.f;
+    }
+    f32x4 st[4];
+    scores<DH>(Ks, qf, wave, g, j16, st);
+    scores<DH>(Vs, gof, wave, g, j16, ds);     // ds[t][reg] = dP~[row][key 16t + 4g + reg] for now
+    const float lse = rok ? a.lse_in[bh * L + row] : 0.f;
+    float delta = 0.f;
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      float m[4] = {1.f, 1.f, 1.f, 1.f};
+      if (rok && t <= wave) drop_mult4(a, bh, row, t, g, m);
+#pragma unroll
+      for (int reg = 0; reg < 4; ++reg) {
+#pragma clang fp contract(off)    // dp is rounded before dp - delta: fused into it, a row whose dS is 0 (L = 1) keeps dust
+        const float p = (rok && 16 * t + 4 * g + reg <= row) ? expf(st[t][reg] - lse) : 0.f;
+        const float dp = ds[t][reg] * m[reg];
+        st[t][reg] = p;
+        ds[t][reg] = dp;
+        pt[t][reg] = p * m[reg];
+        delta += dp * p;
+      }
+    }
+    delta = row_sum4(delta);
+#pragma unroll
+    for (int t = 0; t < 4; ++t)
+#pragma unroll
+      for (int reg = 0; reg < 4; ++reg) {
+#pragma clang fp contract(off)
+        ds[t][reg] = st[t][reg] * (ds[t][reg] - delta) * a.qscale;
+      }
+    f32x4 gq[DH / 16];
+    seam_product<DH>(Ks, ds, wave, g, j16, gq);
+    if (rok) {
+#pragma unroll
+      for (int u = 0; u < DH / 16; ++u)
+        *reinterpret_cast<float4*>(a.gq + base + (int64_t)row * E + 16 * u + 4 * g) =
+            make_float4(gq[u][0], gq[u][1], gq[u][2], gq[u][3]);
+    }
+  }
+  __syncthreads();                      // every wave is done with K and V
+  stage_tile<DH>(Ks, a.q + base, L, E);
+  stage_tile<DH>(Vs, a.go + base, L, E);
+  if (active) {
+#pragma unroll
+    for (int t = 0; t < 4; ++t)
+      if (t <= wave)
+        *reinterpret_cast<float4*>(&Xs[row * kLdX + 16 * t + 4 * g]) = make_float4(pt[t][0], pt[t][1], pt[t][2], pt[t][3]);
+  }
+  __syncthreads();
+  const int key = 16 * wave + j16;
+  f32x4 acc[DH / 16];
+  if (active) {
+    key_tile_product<DH>(Xs, Vs, wave, nT, g, j16, acc);     // dV = P~^T dO
+    if (key < L) {
+#pragma unroll
+      for (int u = 0; u < DH / 16; ++u)
+        *reinterpret_cast<float4*>(a.gv + base + (int64_t)key * E + 16 * u + 4 * g) =
+            make_float4(acc[u][0], acc[u][1], acc[u][2], acc[u][3]);
+    }
+  }
+  __syncthreads();
+  if (active) {
+#pragma unroll
+    for (int t = 0; t < 4; ++t)
+      if (t <= wave)
+        *reinterpret_cast<float4*>(&Xs[row * kLdX + 16 * t + 4 * g]) = make_float4(ds[t][0], ds[t][1], ds[t][2], ds[t][3]);
+  }
+  __syncthreads();
+  if (active) {
+    key_tile_product<DH>(Xs, Ks, wave, nT, g, j16, acc);     // dK = dS^T Q  (dS carries 1 / sqrt(dh))
+    if (key < L) {
+#pragma unroll
+      for (int u = 0; u < DH / 16; ++u)
+        *reinterpret_cast<float4*>(a.gk + base + (int64_t)key * E + 16 * u + 4 * g) =
+            make_float4(acc[u][0], acc[u][1], acc[u][2], acc[u][3]);
+    }
+  }
+}
+
+srh_status_t attn_check(const char* what, int64_t B, int32_t L, int32_t H, int32_t dh, const uint8_t* d_keep,
+                        float drop_p, AttnArgs& a) {
+  SRH_REQUIRE(B >= 1 && L >= 1 && H >= 1, "%s: bad shape B=%lld L=%d H=%d", what, (long long)B, L, H);
+  SRH_REQUIRE(drop_p >= 0.f && drop_p < 1.f, "%s: drop probability must be in [0, 1)", what);
+  SRH_SUPPORTED(L <= kMaxL, "%s: L=%d -- the kernel holds sequences of up to %d positions", what, L, kMaxL);
+  SRH_SUPPORTED(dh == 32 || dh == 64, "%s: head width %d -- the kernel serves 32 and 64", what, dh);
+  SRH_SUPPORTED((int64_t)H * dh <= 128, "%s: H dh = %lld -- the kernel serves up to 128", what, (long long)H * dh);
+  SRH_SUPPORTED(B * H < (int64_t(1) << 31) && B * L * H * dh < (int64_t(1) << 40), "%s: too many sequences", what);
+  a.L = L; a.H = H; a.keep = d_keep;
+  a.drop = d_keep ? DROP_GIVEN : (drop_p > 0.f ? DROP_DRAWN : DROP_NONE);
+  a.drop_p = drop_p;
+  a.drop_scale = 1.f / (1.f - drop_p);
+  a.qscale = 1.f / sqrtf((float)dh);
+  return SRH_OK;
+}
+
+// ---- BCE ---------------------------------------------------------------------------------------------------------------
+// one wave per hidden row
+__global__ __launch_bounds__(256) void bce_rows(const float* __restrict__ hid, int64_t R, int32_t d,
+                                                const float* __restrict__ table, int64_t n_table,
+                                                const int32_t* __restrict__ pos, const int32_t* __restrict__ neg,
+                                                const uint8_t* __restrict__ valid, double inv_n, double* __restrict__ terms,
+                                                float* __restrict__ gh, float* __restrict__ grows) {
+  const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  if (r >= R) return;
+  const int64_t p = pos[r], n = neg[r];
+  const bool ok = valid[r] != 0 && p >= 0 && p < n_table && n >= 0 && n < n_table;
+  if (!ok) {
+    for (int c = lane; c < d; c += 64) gh[r * d + c] = grows[r * d + c] = grows[(R + r) * d + c] = 0.f;
+    if (lane == 0) terms[r] = terms[R + r] = 0.0;
+    return;
+  }
+  float dp = 0.f, dn = 0.f;
+  for (int c = lane; c < d; c += 64) {
+    const float hv = hid[r * d + c];
+    dp = fmaf(hv, table[p * d + c], dp);
+    dn = fmaf(hv, table[n * d + c], dn);
+  }
+  const double xp = (double)wave_sum_f(dp), xn = (double)wave_sum_f(dn);
+  // BCE with logits, stable: max(x, 0) - x y + log1p(exp(-|x|));  d/dx = sigmoid(x) - y
+  const double ep = exp(-fabs(xp)), en = exp(-fabs(xn));
+  const double lp = fmax(xp, 0.0) - xp + log1p(ep), ln = fmax(xn, 0.0) + log1p(en);
+  const double sp = xp >= 0.0 ? 1.0 / (1.0 + ep) : ep / (1.0 + ep), sn = xn >= 0.0 ? 1.0 / (1.0 + en) : en / (1.0 + en);
+  const float cp = (float)((sp - 1.0) * inv_n), cn = (float)(sn * inv_n);
+  for (int c = lane; c < d; c += 64) {
+    const float hv = hid[r * d + c];
+    gh[r * d + c] = fmaf(cp, table[p * d + c], cn * table[n * d + c]);
+    grows[r * d + c] = cp * hv;
+    grows[(R + r) * d + c] = cn * hv;
+  }
+  if (lane == 0) { terms[r] = lp; terms[R + r] = ln; }
+}
+
+// loss[0] / loss[1] = the mean of the positive / negative terms: thread i sums rows i, i + 256, ... ascending, then a
+// fixed tree over the 256 partials
+__global__ __launch_bounds__(256) void bce_reduce(const double* __restrict__ terms, int64_t R, double inv_n,
+                                                  double* __restrict__ loss) {
+  __shared__ double sp[256], sn[256];
+  double a = 0.0, b = 0.0;
+  for (int64_t r = threadIdx.x; r < R; r += 256) { a += terms[r]; b += terms[R + r]; }
+  sp[threadIdx.x] = a; sn[threadIdx.x] = b;
+  __syncthreads();
+  for (int w = 128; w > 0; w >>= 1) {
+    if ((int)threadIdx.x < w) { sp[threadIdx.x] += sp[threadIdx.x + w]; sn[threadIdx.x] += sn[threadIdx.x + w]; }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) { loss[0] = sp[0] * inv_n; loss[1] = sn[0] * inv_n; }
+}
+
+}  // namespace
+
+extern "C" {
+
+srh_status_t srh_seq_attn_fwd_f32(const float* d_q, const float* d_k, const float* d_v, int64_t B, int32_t L, int32_t H,
+                                  int32_t dh, const uint8_t* d_keep, uint64_t rng_seed, uint64_t rng_counter, float drop_p,
+                                  float* d_out, float* d_lse, void* stream) {
+  SRH_REQUIRE(d_q && d_k && d_v && d_out && d_lse, "seq_attn_fwd: null argument");
+  AttnArgs a{};
+  const srh_status_t s = attn_check("seq_attn_fwd", B, L, H, dh, d_keep, drop_p, a);
+  if (s != SRH_OK) return s;
+  a.q = d_q; a.k = d_k; a.v = d_v; a.out = d_out; a.lse = d_lse;
+  a.seed_lo = (uint32_t)rng_seed; a.seed_hi = (uint32_t)(rng_seed >> 32); a.ctr = rng_counter;
+  const unsigned grid = (unsigned)(B * H);
+  if (dh == 64) attn_fwd<64><<<grid, 256, 0, as_stream(stream)>>>(a);
+  else attn_fwd<32><<<grid, 256, 0, as_stream(stream)>>>(a);
+  SRH_LAUNCH_CHECK();
+  return SRH_OK;
+}
+
+srh_status_t srh_seq_attn_bwd_f32(const float* d_q, const float* d_k, const float* d_v, const float* d_go,
+                                  const float* d_lse, int64_t B, int32_t L, int32_t H, int32_t dh, const uint8_t* d_keep,
+                                  uint64_t rng_seed, uint64_t rng_counter, float drop_p, float* d_gq, float* d_gk,
+                                  float* d_gv, void* stream) {
+  SRH_REQUIRE(d_q && d_k && d_v && d_go && d_lse && d_gq && d_gk && d_gv, "seq_attn_bwd: null argument");
+  AttnArgs a{};
+  const srh_status_t s = attn_check("seq_attn_bwd", B, L, H, dh, d_keep, drop_p, a);
+  if (s != SRH_OK) return s;
+  a.q = d_q; a.k = d_k; a.v = d_v; a.go = d_go; a.lse_in = d_lse; a.gq = d_gq; a.gk = d_gk; a.gv = d_gv;
+  a.seed_lo = (uint32_t)rng_seed; a.seed_hi = (uint32_t)(rng_seed >> 32); a.ctr = rng_counter;
+  const unsigned grid = (unsigned)(B * H);
+  if (dh == 64) attn_bwd<64><<<grid, 256, 0, as_stream(stream)>>>(a);
+  else attn_bwd<32><<<grid, 256, 0, as_stream(stream)>>>(a);
+  SRH_LAUNCH_CHECK();
+  return SRH_OK;
+}
+
+int64_t srh_seq_bce_ws_bytes(int64_t R) { return R > 0 ? align256(16 * R) : 0; }
+
+srh_status_t srh_seq_bce_fwd_bwd(const float* d_hidden, int64_t R, int32_t d, const float* d_table, int64_t n_table,
+                                 const int32_t* d_pos, const int32_t* d_neg, const uint8_t* d_valid, int64_t n_valid,
+                                 double* d_loss2, float* d_gh, float* d_grows, void* d_ws, void* stream) {
+  SRH_REQUIRE(d_hidden && d_table && d_pos && d_neg && d_valid && d_loss2 && d_gh && d_grows && d_ws,
+              "seq_bce: null argument");
+  SRH_REQUIRE(R > 0 && R < (int64_t(1) << 30) && d > 0 && d <= 1024 && n_table > 0, "seq_bce: bad sizes");
+  SRH_REQUIRE(n_valid > 0 && n_valid <= R, "seq_bce: n_valid=%lld must be in [1, R]", (long long)n_valid);
+  hipStream_t st = as_stream(stream);
+  double* terms = static_cast<double*>(d_ws);
+  const double inv_n = 1.0 / (double)n_valid;
+  bce_rows<<<(unsigned)((R + 3) / 4), 256, 0, st>>>(d_hidden, R, d, d_table, n_table, d_pos, d_neg, d_valid, inv_n, terms,
+                                                     d_gh, d_grows);
+  SRH_LAUNCH_CHECK();
+  bce_reduce<<<1, 256, 0, st>>>(terms, R, inv_n, d_loss2);
+  SRH_LAUNCH_CHECK();
+  return SRH_OK;
+}
+
+}  // extern "C"

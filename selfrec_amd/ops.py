@@ -25,8 +25,9 @@ __all__ = ["Sampler", "DeviceCSR", "column_class_order", "spmm", "spmm_any", "pa
            "axpby", "batch_fetch", "zero_rows", "cursor_advance", "batch_lists", "batch_pack", "batch_unpack", "batch_scatter",
            "table_nce_ws", "table_nce_fwd_bwd", "kmeans_assign", "kmeans_update", "kmeans",
            "find_k_largest_host_f64", "knn_neighbours", "knn_score_ws", "knn_score_topk",
-           "tower_fwd", "tower_bwd", "scatter_plan", "rows_segment_sum", "batch_softmax_fwd_bwd", "TowerFn",
-           "BatchSoftmaxFn", "SelfrecHipError"]
+           "tower_fwd", "tower_bwd", "scatter_plan", "scatter_plan_host", "rows_segment_sum", "batch_softmax_fwd_bwd", "TowerFn",
+           "BatchSoftmaxFn", "seq_attn_supported", "seq_attn_fwd", "seq_attn_bwd", "SeqAttnFn", "seq_bce_fwd_bwd", "SeqBceFn",
+           "GatherRowsFn", "SelfrecHipError"]
 
 
 def _stream() -> int:
@@ -1337,14 +1338,19 @@ def tower_bwd(saved, y, gy, w1, b1, w2, b2, *, mask_row0=None, drop_p=0.0, ws=No
 def scatter_plan(ids, device):
     """The segments of srh_rows_segment_sum_f32 for gathered-row ids (host array): a stable sort of the rows by id, so
     each table row sums its rows in ascending row order.  -> (order, seg_start, seg_row) int32 device tensors."""
+    to = lambda a: torch.from_numpy(a).to(device)  # noqa: E731
+    return tuple(to(a) for a in scatter_plan_host(ids))
+
+
+def scatter_plan_host(ids):
+    """scatter_plan's three int32 arrays on the host, for a caller that uploads them with its batch"""
     ids = np.ascontiguousarray(np.asarray(ids).reshape(-1), dtype=np.int64)
     order = np.argsort(ids, kind="stable")
     s = ids[order]
     first = np.flatnonzero(np.r_[True, s[1:] != s[:-1]]) if s.size else np.zeros(0, dtype=np.int64)
     seg_start = np.r_[first, s.size].astype(np.int32)
     seg_row = s[first].astype(np.int32)
-    to = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(device)  # noqa: E731
-    return to(order), to(seg_start), to(seg_row)
+    return tuple(np.ascontiguousarray(a, dtype=np.int32) for a in (order, seg_start, seg_row))
 
 
 def rows_segment_sum(x, plan, out):
@@ -1425,3 +1431,140 @@ class TowerFn(torch.autograd.Function):
             plan = ctx.plan if ctx.plan is not None else scatter_plan(ctx.idx.cpu().numpy(), table.device)
             gt = rows_segment_sum(gx, plan, torch.zeros_like(table))
         return gt, gw1, gb1, gw2, gb2, None, None, None, None, None, None, None, None
+
+
+# ---- SASRec (csrc/seqrec.hip) ------------------------------------------------------------------------------------------
+SEQ_ATTN_MAX_LEN = 64                         # srh_seq_attn_*: L <= 64, dh in SEQ_ATTN_HEAD_WIDTHS, H dh <= 128
+SEQ_ATTN_HEAD_WIDTHS = (32, 64)
+SEQ_ATTN_MAX_WIDTH = 128
+
+
+def seq_attn_supported(L: int, H: int, dh: int) -> bool:
+    """whether (L, H, dh) is inside the fused attention kernel's envelope (include/selfrec_hip.h)"""
+    return 1 <= L <= SEQ_ATTN_MAX_LEN and dh in SEQ_ATTN_HEAD_WIDTHS and 1 <= H and H * dh <= SEQ_ATTN_MAX_WIDTH
+
+
+def _attn_shape(q, k, v, n_heads):
+    if q.dim() != 3 or q.shape != k.shape or q.shape != v.shape:
+        raise SelfrecHipError("seq_attn: q, k, v must be (B, L, H * dh) tensors of one shape")
+    B, L, E = (int(s) for s in q.shape)
+    H = int(n_heads)
+    if H < 1 or E % H:
+        raise SelfrecHipError(f"seq_attn: width {E} does not split into {H} heads")
+    return B, L, H, E // H
+
+
+def _attn_keep(keep, B, H, L):
+    if keep is None:
+        return None
+    if tuple(keep.shape) != (B, H, L, L):
+        raise SelfrecHipError(f"seq_attn: keep mask of shape {tuple(keep.shape)}, expected {(B, H, L, L)}")
+    return keep.to(torch.uint8).contiguous()
+
+
+def seq_attn_fwd(q, k, v, n_heads, *, keep=None, drop_p=0.0, rng_seed=0, rng_counter=0):
+    """Causal attention of projected q, k, v (B, L, H * dh): (out (B, L, H * dh), lse (B, H, L)).  Dropout on the
+    probabilities: ``keep`` ((B, H, L, L), 1 = keep) replays a given mask; without it and with drop_p > 0 the mask is
+    drawn in-kernel at the counters [rng_counter, rng_counter + B * H * L) (include/selfrec_hip.h)."""
+    B, L, H, dh = _attn_shape(q, k, v, n_heads)
+    keep = _attn_keep(keep, B, H, L)
+    out = torch.empty_like(q)
+    lse = torch.empty((B, H, L), dtype=torch.float32, device=q.device)
+    check(_lib.load().srh_seq_attn_fwd_f32(_p(q, torch.float32, "q"), _p(k, torch.float32, "k"), _p(v, torch.float32, "v"),
+                                           B, L, H, dh, _p(keep, torch.uint8, "keep"),
+                                           int(rng_seed) & 0xFFFFFFFFFFFFFFFF, int(rng_counter) & 0xFFFFFFFFFFFFFFFF,
+                                           float(drop_p), _p(out), _p(lse), _stream()), "srh_seq_attn_fwd_f32")
+    return out, lse
+
+
+def seq_attn_bwd(q, k, v, lse, go, n_heads, *, keep=None, drop_p=0.0, rng_seed=0, rng_counter=0):
+    """(dq, dk, dv) of seq_attn_fwd for the upstream gradient go, with the forward's dropout arguments."""
+    B, L, H, dh = _attn_shape(q, k, v, n_heads)
+    keep = _attn_keep(keep, B, H, L)
+    go = go.to(torch.float32).contiguous()
+    gq, gk, gv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
+    check(_lib.load().srh_seq_attn_bwd_f32(_p(q, torch.float32, "q"), _p(k, torch.float32, "k"), _p(v, torch.float32, "v"),
+                                           _p(go, torch.float32, "go"), _p(lse, torch.float32, "lse"), B, L, H, dh,
+                                           _p(keep, torch.uint8, "keep"), int(rng_seed) & 0xFFFFFFFFFFFFFFFF,
+                                           int(rng_counter) & 0xFFFFFFFFFFFFFFFF, float(drop_p), _p(gq), _p(gk), _p(gv),
+                                           _stream()), "srh_seq_attn_bwd_f32")
+    return gq, gk, gv
+
+
+class SeqAttnFn(torch.autograd.Function):
+    """seq_attn_fwd / seq_attn_bwd as one differentiable op of (q, k, v)."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, n_heads, keep, drop_p, rng_seed, rng_counter):
+        q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
+        out, lse = seq_attn_fwd(q, k, v, n_heads, keep=keep, drop_p=drop_p, rng_seed=rng_seed, rng_counter=rng_counter)
+        ctx.save_for_backward(q, k, v, lse)
+        ctx.args = (n_heads, keep, drop_p, rng_seed, rng_counter)
+        return out
+
+    @staticmethod
+    def backward(ctx, go):
+        q, k, v, lse = ctx.saved_tensors
+        n_heads, keep, drop_p, rng_seed, rng_counter = ctx.args
+        gq, gk, gv = seq_attn_bwd(q, k, v, lse, go, n_heads, keep=keep, drop_p=drop_p, rng_seed=rng_seed,
+                                  rng_counter=rng_counter)
+        return gq, gk, gv, None, None, None, None, None
+
+
+def seq_bce_fwd_bwd(hidden, table, pos, neg, valid, n_valid=None, ws=None):
+    """SASRec.calculate_loss over hidden rows (R x d): (loss2 (2,) float64: the positive and the negative
+    BCE-with-logits means over the rows with valid != 0, dL/dhidden (R x d), per-row table gradients (2R x d: rows of
+    pos, then of neg)).  pos / neg: int32 item ids, valid: uint8, all of R entries on the device."""
+    if hidden.dim() != 2 or table.dim() != 2 or hidden.shape[1] != table.shape[1]:
+        raise SelfrecHipError("seq_bce: hidden (R x d) and table (n x d) expected")
+    R, d = int(hidden.shape[0]), int(hidden.shape[1])
+    for t, name in ((pos, "pos"), (neg, "neg"), (valid, "valid")):
+        if int(t.numel()) != R:
+            raise SelfrecHipError(f"seq_bce: {name} has {int(t.numel())} entries, expected {R}")
+    if n_valid is None:
+        n_valid = int(valid.count_nonzero().item())
+    dev = hidden.device
+    need = int(_lib.load().srh_seq_bce_ws_bytes(R))
+    if ws is None or ws.numel() * ws.element_size() < need:
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    loss2 = torch.empty(2, dtype=torch.float64, device=dev)
+    gh = torch.empty((R, d), dtype=torch.float32, device=dev)
+    grows = torch.empty((2 * R, d), dtype=torch.float32, device=dev)
+    check(_lib.load().srh_seq_bce_fwd_bwd(_p(hidden, torch.float32, "hidden"), R, d, _p(table, torch.float32, "table"),
+                                          int(table.shape[0]), _p(pos, torch.int32, "pos"), _p(neg, torch.int32, "neg"),
+                                          _p(valid, torch.uint8, "valid"), int(n_valid), _p(loss2), _p(gh), _p(grows),
+                                          _p(ws), _stream()), "srh_seq_bce_fwd_bwd")
+    return loss2, gh, grows
+
+
+class SeqBceFn(torch.autograd.Function):
+    """The two BCE means of SASRec.calculate_loss as one kernel call; the item table's gradient is the deterministic
+    segment sum of the per-row gradients (``plan`` = scatter_plan([pos; neg]))."""
+
+    @staticmethod
+    def forward(ctx, hidden, table, pos, neg, valid, n_valid, plan):
+        loss2, gh, grows = seq_bce_fwd_bwd(hidden.contiguous(), table, pos, neg, valid, n_valid)
+        ctx.save_for_backward(gh, grows)
+        ctx.plan, ctx.table_shape = plan, tuple(table.shape)
+        return (loss2[0].to(torch.float32) + loss2[1].to(torch.float32))
+
+    @staticmethod
+    def backward(ctx, gout):
+        gh, grows = ctx.saved_tensors
+        gt = rows_segment_sum(grows, ctx.plan, torch.zeros(ctx.table_shape, dtype=torch.float32, device=gh.device))
+        return gh * gout, gt * gout, None, None, None, None, None
+
+
+class GatherRowsFn(torch.autograd.Function):
+    """table[idx] whose table gradient is the deterministic segment sum (``plan`` = scatter_plan(idx)) instead of an
+    atomic index_add."""
+
+    @staticmethod
+    def forward(ctx, table, idx, plan):
+        ctx.plan, ctx.table_shape = plan, tuple(table.shape)
+        return table[idx.long()]
+
+    @staticmethod
+    def backward(ctx, g):
+        g2 = g.reshape(-1, ctx.table_shape[1]).to(torch.float32).contiguous()
+        return rows_segment_sum(g2, ctx.plan, torch.zeros(ctx.table_shape, dtype=torch.float32, device=g.device)), None, None

@@ -108,3 +108,58 @@ def write_text(path: str, users: np.ndarray, items: np.ndarray, weight: int = 1)
     """``"user item weight"`` lines, the on-disk format of reference data/loader.py:26-32."""
     with open(path, "w") as f:
         f.writelines(f"{a} {b} {weight}\n" for a, b in zip(users.tolist(), items.tolist()))
+
+
+# ---- sequence datasets (model.type: sequential) -----------------------------------------------------------------------
+# name -> (n_sequences, n_items, n_interactions_total)   [train + the one held-out item per sequence]
+SEQ_SHAPES = {
+    # the size of the 5-core Amazon Beauty set conf/SASRec.yaml names (22,363 users, 12,101 items, 198,502 interactions);
+    # the counts are this project's choice, stated in DESIGN.md 4.9
+    "beauty-seq": (22363, 12101, 198502),
+    "tiny-seq": (300, 200, 3600),
+}
+
+
+def generate_sequences(n_seq: int, n_items: int, n_total: int, seed: int = 2024, min_len: int = 3, item_exp: float = 0.8,
+                       follow: float = 0.6):
+    """List of int64 item-id arrays, one per sequence: lengths min_len + a geometric tail summing to ~n_total, items from
+    a Zipf popularity, and with probability ``follow`` the next item is a fixed successor of the current one -- a
+    first-order structure a next-item model can learn.  Every item occurs at least once."""
+    rng = np.random.default_rng(seed)
+    mean_tail = max(n_total / n_seq - min_len, 0.0)
+    lens = min_len + (rng.geometric(1.0 / (1.0 + mean_tail), size=n_seq) - 1 if mean_tail > 0 else np.zeros(n_seq, np.int64))
+    ci = np.cumsum(_zipf_weights(n_items, item_exp, rng))
+    ci[-1] = 1.0
+    successor = rng.permutation(n_items)
+    seqs = []
+    for n in lens.tolist():
+        fresh = np.searchsorted(ci, rng.random(n), side="right")
+        chain = rng.random(n) < follow
+        s = np.empty(n, dtype=np.int64)
+        s[0] = fresh[0]
+        for t in range(1, n):
+            s[t] = successor[s[t - 1]] if chain[t] else fresh[t]
+        seqs.append(s)
+    # every item at least once: the missing ones replace inner positions of the longest sequences
+    missing = np.setdiff1d(np.arange(n_items), np.unique(np.concatenate(seqs)))
+    order = np.argsort(-lens, kind="stable")
+    for k, it in enumerate(missing.tolist()):
+        s = seqs[order[k % n_seq]]
+        s[(k // n_seq) % max(len(s) - 1, 1)] = it
+    return seqs
+
+
+def make_sequence_dataset(shape: str = "tiny-seq", seed: int = 2024):
+    """(train, test): {seq_name: [item_name, ...]} dicts in the loader's in-memory format; leave-one-out -- the last item
+    of every sequence is its test item."""
+    n_seq, n_items, n_total = SEQ_SHAPES[shape]
+    seqs = generate_sequences(n_seq, n_items, n_total, seed)
+    train = {str(k): [str(i) for i in s[:-1].tolist()] for k, s in enumerate(seqs)}
+    test = {str(k): [str(int(s[-1]))] for k, s in enumerate(seqs)}
+    return train, test
+
+
+def write_sequences(path: str, sequences) -> None:
+    """``"seq_id:item item ..."`` lines, the on-disk format of reference data/loader.py:35-41."""
+    with open(path, "w") as f:
+        f.writelines(f"{name}:{' '.join(items)}\n" for name, items in sequences.items())

@@ -7,6 +7,8 @@ the reference would leave it (after every batch, so interleaved ``random`` calls
 caller see the same stream), and shuffles ``data.training_data`` in place into the same
 order.
 """
+import random as _pyrandom
+
 import numpy as np
 
 from .. import ops
@@ -100,3 +102,55 @@ def next_batch_pairwise(data, batch_size, n_negs=1, as_arrays=False):
             if fastpath.active():             # (dropin.install(): the lists' device copies, uploaded once -- util/fastpath.py)
                 fastpath.register_batch(lists, (u, i, j))
             yield lists
+
+
+# ---- sequential models (reference util/sampler.py:84-133) ----------------------------------------------------------------
+def _window(n_items, max_len, training):
+    """(start, end) of a sequence's slice: the last max_len items of a longer one.  A training row keeps end = its
+    length - 1 inputs (the last item is only a target); the reference cuts a longer one to max_len - 1 inputs."""
+    if n_items > max_len:
+        return -max_len, (max_len - 1 if training else max_len)
+    return 0, (n_items - 1 if training else n_items)
+
+
+def next_batch_sequence(data, batch_size, n_negs=1, max_len=50):
+    """Batches (seq, pos, y, neg, seq_len) of one epoch, (rows, max_len) int arrays padded with 0 on the right.
+
+    Consumes python's global ``random`` exactly as the reference does: one ``shuffle`` of the id lists, then per sequence
+    one ``sample(item_list, end)``, drawn again while it shares an item with the sequence's INPUT slice -- so after an
+    epoch the generator state, and every batch, equal the reference's."""
+    rows = [ids for _, ids in data.original_seq]
+    _pyrandom.shuffle(rows)
+    item_list = list(range(1, data.item_num + 1))
+    for lo in range(0, len(rows), batch_size):
+        chunk = rows[lo:lo + batch_size]
+        seq, pos, y, neg = (np.zeros((len(chunk), max_len), dtype=int) for _ in range(4))
+        seq_len = []
+        for n, ids in enumerate(chunk):
+            start, end = _window(len(ids), max_len, True)
+            inputs = ids[start:-1]
+            seq[n, :end] = inputs
+            pos[n, :end] = np.arange(1, end + 1)
+            y[n, :end] = ids[start + 1:]
+            seen = set(inputs)
+            negatives = _pyrandom.sample(item_list, end)
+            while not seen.isdisjoint(negatives):
+                negatives = _pyrandom.sample(item_list, end)
+            neg[n, :end] = negatives
+            seq_len.append(end)
+        yield seq, pos, y, neg, np.array(seq_len, int)
+
+
+def next_batch_sequence_for_test(data, batch_size, max_len=50):
+    """Batches (seq, pos, seq_len) over data.original_seq in its order: every sequence's last max_len items."""
+    rows = [ids for _, ids in data.original_seq]
+    for lo in range(0, len(rows), batch_size):
+        chunk = rows[lo:lo + batch_size]
+        seq, pos = (np.zeros((len(chunk), max_len), dtype=int) for _ in range(2))
+        seq_len = []
+        for n, ids in enumerate(chunk):
+            start, end = _window(len(ids), max_len, False)
+            seq[n, :end] = ids[start:]
+            pos[n, :end] = np.arange(1, end + 1)
+            seq_len.append(end)
+        yield seq, pos, np.array(seq_len, int)
