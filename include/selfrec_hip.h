@@ -531,7 +531,8 @@ srh_status_t srh_score_mask_topk(const float* d_user_emb, const int32_t* d_user_
  * Scores come from the same fma chain, so ids and scores are identical to srh_score_mask_topk.
  * d_out_counts[q] = number of survivors of row q, training items included: when it exceeds `cap`
  * (tie-heavy rows, users with thousands of training items) that row of the outputs is NOT valid and the caller ranks it with
- * srh_score_mask_topk.  d_ws: srh_score_mask_topk_filtered_ws_bytes(chunk_rows, ...) bytes.
+ * srh_score_mask_topk.  Any k <= cap <= 4096 is served, small ones included: a row is ranked iff its count is <= cap, and a row
+ * that is not ranked is not read either.  d_ws: srh_score_mask_topk_filtered_ws_bytes(chunk_rows, ...) bytes.
  * Shape constants measured on the Yelp2018 shape (profiles/r03_m_*): chunk_rows 16384 (larger chunks fill the chip: 4096 ->
  * 16384 users per chunk is +20 %), sample_items 3072 in norm order (2048 .. 4096 are within 3 % of each other on trained
  * tables; round 3, catalogue order: 4096), cap 1024.  In the split path, pass 1 derives t~_u as the K-th largest of 256 disjoint group maxima of

@@ -695,6 +695,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8))) voi
 // (a wave's LDS operations complete in order), the counters of the compactions are wave-uniform registers, membership in
 // the user's training row is a binary search in an LDS copy of that row (rows longer than TRW: in global memory), and
 // 24 rows are in flight per CU.  Same arithmetic, same order of the exact fma chain, same (score desc, id asc) ranking.
+// A list is this kernel's only if it is short AND complete: c <= min(CW, cap).  With cap < CW (the API allows any
+// k <= cap <= 4096) a row with cap < c <= CW has overflowed -- slots t >= cap were never written and the words there belong
+// to the next row or to nobody -- and is left alone, reported through its count, like everywhere else.  (The first version
+// tested c > CW only: such a row took item ids from foreign or unwritten workspace words and read item_norm[id], I + id * D
+// with them.  Production's cap = 1024 never took that path.  The other readers of cnt were checked with it: both flushes
+// store under slot < cap, cand_topk_kernel and rescore_topk_kernel return on c > cap, and rescore_topk_kernel's
+// c <= skip_upto hands over exactly the complete short lists this kernel takes.)
 template <int D, int CW>
 __global__ __launch_bounds__(256) void rescore_wave_kernel(const float* __restrict__ U, const int32_t* __restrict__ user_ids, int user_base,
                                                            const float* __restrict__ I, int rows, const int32_t* __restrict__ cnt,
@@ -714,7 +721,7 @@ __global__ __launch_bounds__(256) void rescore_wave_kernel(const float* __restri
   const int row = blockIdx.x * 4 + w;
   if (row >= rows) return;
   const int c = cnt[row];
-  if (c > CW) return;                                             // (long or overflowed lists: rescore_topk_kernel)
+  if (c > CW || c > cap) return;                                  // (long lists: rescore_topk_kernel; overflowed ones: nobody)
   float* s_val = s_val_[w];
   float* s_dl = s_dl_[w];
   int* s_idx = s_idx_[w];
