@@ -887,6 +887,37 @@ srh_status_t srh_seq_bce_fwd_bwd(const float* d_hidden, int64_t R, int32_t d, co
                                  double* d_loss2, float* d_gh, float* d_grows, void* d_ws, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * (a-17) BERT4Rec -- replaces the attention core of nn.MultiheadAttention as model/sequential/BERT4Rec.py:123 calls it
+ * (attn_mask=None, no key-padding mask) and calculate_loss (BERT4Rec.py:58-62).
+ *
+ * srh_seq_attn_full_fwd_f32 / srh_seq_attn_full_bwd_f32: the arguments, layouts, dropout contract (keep mask given, or
+ *   drawn at counter rng_counter + (b H + h) L + row, float4 col / 4, word col % 4; B H L counters per call), envelope
+ *   and repeatability of srh_seq_attn_fwd_f32 / _bwd_f32 of (a-16), with P = softmax_j(q_i . k_j / sqrt(dh)) over ALL
+ *   0 <= j < L: out[b, i, h] = sum_{j < L} P~[b, h, i, j] v[b, j, h].  Every position takes part, padded ones included.
+ * srh_table_ce_fwd_bwd: softmax cross-entropy of the rows d_h (M x d) against the whole table d_t (N x d), logits
+ *   s_mj = h_m . t_j (no normalisation, no temperature), d_labels (M, int32, in [0, N)):
+ *     d_loss[0] = loss_scale * sum_m (lse_m - s_{m, label_m}),  lse_m = log sum_j exp(s_mj)   (double, fixed order)
+ *     d_gh (M x d)        = loss_scale * (sum_j P_mj t_j - t_{label_m}),  P_mj = exp(s_mj - lse_m)
+ *     d_gt (N x d, dense) = loss_scale * sum_m (P_mj - [j == label_m]) h_m
+ *   all three WRITTEN.  The M x N logits and probabilities never reach memory; the softmax is max-subtracted (safe for
+ *   any finite logits); no float atomics: one producer and one summation order per output element, the same bits on
+ *   every call.  d = 64 or 128 (the caller zero-pads narrower rows), else SRH_ERR_UNSUPPORTED with a message; any M >= 1,
+ *   N >= 1.  A label outside [0, N) reads nothing and makes the loss NaN.  d_ws >= srh_table_ce_ws_bytes(M, N, d).
+ *   F.cross_entropy(h @ t.T, labels) / M (BERT4Rec.py:61) is loss_scale = 1 / M^2.
+ * ---------------------------------------------------------------------------------- */
+srh_status_t srh_seq_attn_full_fwd_f32(const float* d_q, const float* d_k, const float* d_v, int64_t B, int32_t L,
+                                       int32_t H, int32_t dh, const uint8_t* d_keep, uint64_t rng_seed,
+                                       uint64_t rng_counter, float drop_p, float* d_out, float* d_lse, void* stream);
+srh_status_t srh_seq_attn_full_bwd_f32(const float* d_q, const float* d_k, const float* d_v, const float* d_go,
+                                       const float* d_lse, int64_t B, int32_t L, int32_t H, int32_t dh,
+                                       const uint8_t* d_keep, uint64_t rng_seed, uint64_t rng_counter, float drop_p,
+                                       float* d_gq, float* d_gk, float* d_gv, void* stream);
+int64_t srh_table_ce_ws_bytes(int64_t M, int64_t N, int32_t d);
+srh_status_t srh_table_ce_fwd_bwd(const float* d_h, int64_t M, const float* d_t, int64_t N, int32_t d,
+                                  const int32_t* d_labels, float loss_scale, double* d_loss, float* d_gh, float* d_gt,
+                                  void* d_ws, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * (f-1) Dataset files -> id arrays -- replaces the python loops of data/loader.py:22-33
  * (FileIO.load_data_set: one "user item weight" line per interaction, single-space separated)
  * and data/ui_graph.py:29-45 (ids in first-appearance order of the training file; test pairs kept

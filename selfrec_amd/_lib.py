@@ -182,6 +182,11 @@ SIGNATURES = {
     "srh_seq_attn_fwd_f32": (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _u64, _u64, _f32, _vp, _vp, _vp]),
     "srh_seq_attn_bwd_f32": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _u64, _u64, _f32, _vp, _vp, _vp,
                                     _vp]),
+    "srh_seq_attn_full_fwd_f32": (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _u64, _u64, _f32, _vp, _vp, _vp]),
+    "srh_seq_attn_full_bwd_f32": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _u64, _u64, _f32, _vp, _vp,
+                                         _vp, _vp]),
+    "srh_table_ce_ws_bytes": (_i64, [_i64, _i64, _i32]),
+    "srh_table_ce_fwd_bwd": (_i32, [_vp, _i64, _vp, _i64, _i32, _vp, _f32, _vp, _vp, _vp, _vp, _vp]),
     "srh_seq_bce_ws_bytes": (_i64, [_i64]),
     "srh_seq_bce_fwd_bwd": (_i32, [_vp, _i64, _i32, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
     "srh_adam_step": (_i32, [_vp, _vp, _vp, _vp, _i64, _i64, _vp, _f32, _f32, _f32, _f32, _vp]),

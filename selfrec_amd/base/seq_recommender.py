@@ -1,7 +1,8 @@
 """``SequentialRecommender`` with the surface of reference base/seq_recommender.py:8-83.
 
-``test()`` ranks ``max_N`` over ALL ``item_num + 1`` rows of the item table -- the padding row 0 included, which is then
-dropped from the list, so a list can be one shorter than ``max_N``.  The reference drops it from the NAMES only and zips
+``test()`` ranks ``max_N`` over ALL rows of the item table -- ``item_num + 1`` with the padding row 0 (SASRec),
+``item_num + 2`` with BERT4Rec's mask token behind them -- and then drops ids 0 and ``> item_num`` from the list, so a list
+can be that many names shorter than ``max_N``.  The reference drops it from the NAMES only and zips
 them with the unfiltered scores (seq_recommender.py:49-50): behind row 0's place every name carries its predecessor's
 score.  The lists here are the reference's, that pairing included; the ranking metrics read the names only.  A model that exposes
 ``last_hidden(seq, pos, seq_len)`` and a device ``item_table()`` is scored and ranked on the device: ``ops.gemm_nt`` for
@@ -63,14 +64,15 @@ class SequentialRecommender(Recommender):
     def test(self):
         data = self.data
         names = [name for name, _ in data.original_seq]
-        n_rows = data.item_num + 1
-        on_device = self.max_N + 1 <= min(DEVICE_TOPK_MAX, n_rows) and self.item_table() is not None
+        table = self.item_table()
+        n_rows = data.item_num + 1 if table is None else int(table.shape[0])      # the columns a model scores
+        on_device = table is not None and self.max_N + 1 <= min(DEVICE_TOPK_MAX, n_rows)
         rec_list = {}
         for n, (seq, pos, seq_len) in enumerate(next_batch_sequence_for_test(data, self.batch_size, max_len=self.max_len)):
             block = names[n * self.batch_size:(n + 1) * self.batch_size]
             hidden = self.last_hidden(seq, pos, seq_len) if on_device else None
             if hidden is not None:
-                ids, scores = self._rank_on_device(hidden, self.item_table())
+                ids, scores = self._rank_on_device(hidden, table)
                 ranked = zip(ids.tolist(), scores.tolist())
             else:
                 ranked = (find_k_largest(self.max_N, row) for row in self.predict(seq, pos, seq_len))

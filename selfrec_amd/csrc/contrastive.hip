@@ -29,6 +29,13 @@
 //                                                  the c order inside a k-step is 4*(lane>>4) + reg, matched by A)
 // pass 1: R = queries, C = keys,    W = e                               -> O = sum_j e_bj t_j, and the row sums of W
 // pass 2: R = keys,    C = queries, W = e cw_c - [pos(c) == key] cd_c   -> O = dL/dt / g
+//
+// Softmax cross-entropy of rows against a whole table (srh_table_ce_fwd_bwd, BERT4Rec.py:58-62) is a
+// sibling on the same ownership, seam, chunking and staging: logits s_mj = H_m . T_j with no normalisation and no
+// temperature, so they have no bound and the softmax is max-subtracted.  Pass 1 keeps a running max per row, rescales its
+// sums when a key tile raises it (e = exp(s - max)) and writes (max, sum e, sum e T_j) per key chunk; the finish takes the
+// row's largest chunk max, merges the partials in chunk order with exp(max_c - max), and fixes lse_m; pass 2 weighs with
+// exp(s - lse_m) - [j == label_m] <= 1.  No prep launch: the rows are used as they are.
 #include <algorithm>
 #include <cmath>
 
@@ -362,6 +369,240 @@ srh_status_t launch_ct(CtArgs& a, int np, hipStream_t st) {
   return SRH_OK;
 }
 
+// ---- softmax cross-entropy of M rows against the whole table: unbounded logits, running max --------------------------
+#define SRH_SUPPORTED(cond, ...)         \
+  do {                                   \
+    if (!(cond)) {                       \
+      ::srh::set_error(__VA_ARGS__);     \
+      return SRH_ERR_UNSUPPORTED;        \
+    }                                    \
+  } while (0)
+
+struct CeArgs {
+  const float* h;        // M x D
+  const float* t;        // N x D
+  const int32_t* label;  // M
+  int64_t M, N;
+  float scale;
+  double* loss;
+  float* gh;
+  float* gt;
+  // workspace
+  float* part_o;     // chunks x M x D  sum_j e_mj T_j per key chunk, e = exp(s - part_m)
+  double* part_rs;   // chunks x M      sum_j e_mj per key chunk
+  float* part_m;     // chunks x M      the chunk's largest logit of row m
+  float* lse;        // M               log sum_j exp(s_mj)
+  double* row_loss;  // M               lse_m - s_{m, label_m}
+  int64_t chunks, chunk_len;
+};
+
+inline int64_t ce_ws_bytes(int64_t M, int64_t N, int D) {
+  const int64_t c = ct_chunks(M, N);
+  return align256(4 * c * M * D) + align256(8 * c * M) + align256(4 * c * M) + align256(4 * M) + align256(8 * M);
+}
+
+void ce_carve(CeArgs& a, char* ws, int D) {
+  char* cur = ws;
+  auto take = [&](int64_t bytes) { char* r = cur; cur += align256(bytes); return r; };
+  a.chunks = ct_chunks(a.M, a.N);
+  a.chunk_len = ct_chunk_len(a.M, a.N);
+  a.part_o = (float*)take(4 * a.chunks * a.M * D);
+  a.part_rs = (double*)take(8 * a.chunks * a.M);
+  a.part_m = (float*)take(4 * a.chunks * a.M);
+  a.lse = (float*)take(4 * a.M);
+  a.row_loss = (double*)take(8 * a.M);
+}
+
+// max over the four lanes (lane >> 4 = 0..3) that share an R row: the same bits in all four
+__device__ __forceinline__ float ce_row_max4(float v) {
+  v = fmaxf(v, __shfl_xor(v, 16));
+  v = fmaxf(v, __shfl_xor(v, 32));
+  return v;
+}
+
+// pass 1: R = the rows of H, C = a key chunk of T, W = exp(s - running max)  -> per chunk (max, sum W, sum W T_j)
+// pass 2: R = the rows of T, C = all rows of H,    W = exp(s - lse_c) - [label_c == r]  -> dL/dT_r / scale
+template <int D, bool PASS2>
+__global__ __launch_bounds__(256) void ce_pass(CeArgs P) {
+  constexpr int LDS_STRIDE = D + 4;
+  __shared__ float cs[kCtCTile * LDS_STRIDE];
+  __shared__ float clse[kCtCTile];
+  __shared__ int32_t clab[kCtCTile];
+  const int64_t nR = PASS2 ? P.N : P.M;
+  const float* Rn = PASS2 ? P.t : P.h;
+  const float* Cn = PASS2 ? P.h : P.t;
+  const int64_t rtile = PASS2 ? (int64_t)blockIdx.x : (int64_t)blockIdx.x / P.chunks;
+  const int64_t chunk = PASS2 ? 0 : (int64_t)blockIdx.x % P.chunks;
+  int64_t cbeg = 0, cend = P.M;
+  if (!PASS2) {
+    cbeg = chunk * P.chunk_len;
+    cend = cbeg + P.chunk_len < P.N ? cbeg + P.chunk_len : P.N;
+  }
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, g = lane >> 4, j16 = lane & 15;
+  const int64_t r = rtile * kCtRows + wave * 16 + j16;
+  const bool rok = r < nR;
+
+  float rf[D / 4];  // B operand of MFMA 1: R[r][4s + g]
+#pragma unroll
+  for (int s = 0; s < D / 4; ++s) rf[s] = rok ? Rn[r * D + 4 * s + g] : 0.f;
+  f32x4 o[D / 16];
+#pragma unroll
+  for (int b = 0; b < D / 16; ++b) o[b] = f32x4{0.f, 0.f, 0.f, 0.f};
+  double rs = 0.0;
+  float m = -INFINITY;
+
+  for (int64_t c0 = cbeg; c0 < cend; c0 += kCtCTile) {
+    __syncthreads();
+    for (int e = threadIdx.x; e < kCtCTile * (D / 4); e += 256) {
+      const int i = e / (D / 4), v = e % (D / 4);
+      const int64_t c = c0 + i;
+      const float4 x = c < cend ? reinterpret_cast<const float4*>(Cn + c * D)[v] : srh::f4_zero();
+      *reinterpret_cast<float4*>(&cs[i * LDS_STRIDE + 4 * v]) = x;
+    }
+    if (PASS2 && threadIdx.x < kCtCTile) {
+      const int64_t c = c0 + threadIdx.x;
+      clse[threadIdx.x] = c < cend ? P.lse[c] : INFINITY;      // (a row past M weighs exp(-inf) = 0)
+      clab[threadIdx.x] = c < cend ? P.label[c] : -1;
+    }
+    __syncthreads();
+    f32x4 s[kCtCTile / 16];
+#pragma unroll
+    for (int sub = 0; sub < kCtCTile / 16; ++sub) {
+      f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+      const float* arow = &cs[(sub * 16 + j16) * LDS_STRIDE + g];
+#pragma unroll
+      for (int k = 0; k < D / 4; ++k) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(arow[4 * k], rf[k], acc, 0, 0, 0);
+      s[sub] = acc;  // s[sub][reg] = S^T[c = sub*16 + 4g + reg][r]
+    }
+    if (!PASS2) {
+      // the keys past the chunk's end are -inf before the max; a tile holds at least one key, so the max is finite
+      float mx = -INFINITY;
+#pragma unroll
+      for (int sub = 0; sub < kCtCTile / 16; ++sub)
+#pragma unroll
+        for (int reg = 0; reg < 4; ++reg) {
+          if (c0 + sub * 16 + 4 * g + reg >= cend) s[sub][reg] = -INFINITY;
+          mx = fmaxf(mx, s[sub][reg]);
+        }
+      const float m_new = fmaxf(m, ce_row_max4(mx));
+      const float alpha = expf(m - m_new);  // 0 on the first tile (m = -inf), 1 while the max stands
+      rs *= (double)alpha;
+#pragma unroll
+      for (int b = 0; b < D / 16; ++b) o[b] *= alpha;
+      m = m_new;
+#pragma unroll
+      for (int sub = 0; sub < kCtCTile / 16; ++sub)
+#pragma unroll
+        for (int reg = 0; reg < 4; ++reg) {
+          const float w = expf(s[sub][reg] - m);
+          rs += (double)w;
+          s[sub][reg] = w;
+        }
+    } else {
+#pragma unroll
+      for (int sub = 0; sub < kCtCTile / 16; ++sub)
+#pragma unroll
+        for (int reg = 0; reg < 4; ++reg) {
+          const int ci = sub * 16 + 4 * g + reg;
+          float w = expf(s[sub][reg] - clse[ci]);
+          if ((int64_t)clab[ci] == r) w -= 1.f;
+          s[sub][reg] = w;
+        }
+    }
+#pragma unroll
+    for (int sub = 0; sub < kCtCTile / 16; ++sub)
+#pragma unroll
+      for (int b = 0; b < D / 16; ++b)
+#pragma unroll
+        for (int reg = 0; reg < 4; ++reg)
+          o[b] = __builtin_amdgcn_mfma_f32_16x16x4f32(cs[(sub * 16 + 4 * g + reg) * LDS_STRIDE + 16 * b + j16], s[sub][reg],
+                                                      o[b], 0, 0, 0);
+  }
+  // o[b][reg] = O[r][16b + 4g + reg]
+  if (!PASS2) {
+    rs += __shfl_xor(rs, 16);
+    rs += __shfl_xor(rs, 32);
+    if (!rok) return;
+    const int64_t row = chunk * P.M + r;
+    if (g == 0) {
+      P.part_rs[row] = rs;
+      P.part_m[row] = m;
+    }
+#pragma unroll
+    for (int b = 0; b < D / 16; ++b)
+      reinterpret_cast<float4*>(P.part_o + row * D + 16 * b + 4 * g)[0] = make_float4(o[b][0], o[b][1], o[b][2], o[b][3]);
+  } else {
+    if (!rok) return;
+    const float k = P.scale;
+#pragma unroll
+    for (int b = 0; b < D / 16; ++b)
+      reinterpret_cast<float4*>(P.gt + r * D + 16 * b + 4 * g)[0] =
+          make_float4(k * o[b][0], k * o[b][1], k * o[b][2], k * o[b][3]);
+  }
+}
+
+// per row: the chunk partials merged in chunk order under the row's largest max -> lse, loss term, dL/dH
+template <int D>
+__global__ __launch_bounds__(256) void ce_finish(CeArgs P) {
+  constexpr int LPR = D / 4, RPB = 256 / LPR;
+  const int64_t b = (int64_t)blockIdx.x * RPB + threadIdx.x / LPR;
+  const int lane = threadIdx.x % LPR;
+  if (b >= P.M) return;  // (whole row groups leave together)
+  float mm = -INFINITY;
+  for (int64_t c = 0; c < P.chunks; ++c) mm = fmaxf(mm, P.part_m[c * P.M + b]);
+  double rs = 0.0;
+  float4 o = srh::f4_zero();
+  for (int64_t c = 0; c < P.chunks; ++c) {
+    const float a = expf(P.part_m[c * P.M + b] - mm);
+    rs += P.part_rs[c * P.M + b] * (double)a;
+    o = srh::f4_fma(a, reinterpret_cast<const float4*>(P.part_o + (c * P.M + b) * D)[lane], o);
+  }
+  const int64_t j = P.label[b];
+  const bool jok = j >= 0 && j < P.N;  // (a label outside the table reads nothing and makes the loss NaN)
+  const float4 h = reinterpret_cast<const float4*>(P.h + b * D)[lane];
+  const float4 t = jok ? reinterpret_cast<const float4*>(P.t + j * D)[lane] : srh::f4_zero();
+  double spos = (double)h.x * (double)t.x + (double)h.y * (double)t.y + (double)h.z * (double)t.z + (double)h.w * (double)t.w;
+#pragma unroll
+  for (int w = 1; w < LPR; w <<= 1) spos += __shfl_xor(spos, w);
+  const double lse = (double)mm + log(rs);
+  if (lane == 0) {
+    P.row_loss[b] = jok ? lse - spos : (double)NAN;
+    P.lse[b] = (float)lse;
+  }
+  const float inv_rs = (float)(1.0 / rs), k = P.scale;
+  reinterpret_cast<float4*>(P.gh + b * D)[lane] = make_float4(k * (o.x * inv_rs - t.x), k * (o.y * inv_rs - t.y),
+                                                               k * (o.z * inv_rs - t.z), k * (o.w * inv_rs - t.w));
+}
+
+// the loss: the row terms summed in a fixed order by one workgroup, times the scale
+__global__ __launch_bounds__(256) void ce_loss(CeArgs P) {
+  __shared__ double part[256];
+  double s = 0.0;
+  for (int64_t b = threadIdx.x; b < P.M; b += 256) s += P.row_loss[b];
+  part[threadIdx.x] = s;
+  __syncthreads();
+  for (int w = 128; w > 0; w >>= 1) {
+    if ((int)threadIdx.x < w) part[threadIdx.x] += part[threadIdx.x + w];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) P.loss[0] = (double)P.scale * part[0];
+}
+
+template <int D>
+srh_status_t launch_ce(const CeArgs& a, hipStream_t st) {
+  constexpr int RPB = 256 / (D / 4);
+  const int64_t p1 = (a.M + kCtRows - 1) / kCtRows * a.chunks, p2 = (a.N + kCtRows - 1) / kCtRows;
+  ce_pass<D, false><<<(unsigned)p1, 256, 0, st>>>(a);
+  SRH_LAUNCH_CHECK();
+  ce_finish<D><<<(unsigned)((a.M + RPB - 1) / RPB), 256, 0, st>>>(a);
+  SRH_LAUNCH_CHECK();
+  ce_pass<D, true><<<(unsigned)p2, 256, 0, st>>>(a);
+  SRH_LAUNCH_CHECK();
+  ce_loss<<<1, 256, 0, st>>>(a);
+  SRH_LAUNCH_CHECK();
+  return SRH_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -417,6 +658,26 @@ srh_status_t srh_batch_softmax_fwd_bwd(const float* d_u, const float* d_v, int64
   ct_carve(p, static_cast<char*>(d_ws), d);
   hipStream_t st = srh::as_stream(stream);
   return d == 64 ? launch_ct<64, true>(a, 1, st) : launch_ct<128, true>(a, 1, st);
+}
+
+int64_t srh_table_ce_ws_bytes(int64_t M, int64_t N, int32_t d) {
+  if (M <= 0 || N <= 0 || (d != 64 && d != 128)) return 0;
+  return ce_ws_bytes(M, N, d);
+}
+
+srh_status_t srh_table_ce_fwd_bwd(const float* d_h, int64_t M, const float* d_t, int64_t N, int32_t d,
+                                  const int32_t* d_labels, float loss_scale, double* d_loss, float* d_gh, float* d_gt,
+                                  void* d_ws, void* stream) {
+  SRH_REQUIRE(M > 0 && M < (int64_t(1) << 31) && N > 0 && N < (int64_t(1) << 31), "table_ce_fwd_bwd: bad M / N");
+  SRH_SUPPORTED(d == 64 || d == 128, "table_ce_fwd_bwd: d=%d unsupported (64 or 128; narrower rows are zero-padded)", d);
+  SRH_REQUIRE(d_h && d_t && d_labels && d_loss && d_gh && d_gt && d_ws, "table_ce_fwd_bwd: null argument");
+  SRH_REQUIRE(std::isfinite(loss_scale), "table_ce_fwd_bwd: the loss scale must be finite");
+  CeArgs a{};
+  a.h = d_h; a.t = d_t; a.label = d_labels; a.M = M; a.N = N; a.scale = loss_scale;
+  a.loss = d_loss; a.gh = d_gh; a.gt = d_gt;
+  ce_carve(a, static_cast<char*>(d_ws), d);
+  hipStream_t st = srh::as_stream(stream);
+  return d == 64 ? launch_ce<64>(a, st) : launch_ce<128>(a, st);
 }
 
 }  // extern "C"

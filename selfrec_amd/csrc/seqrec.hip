@@ -17,6 +17,11 @@
 //                         dK = dS^T Q of the keys 16w .. 16w + 15 over the query tiles w .. in ascending order.
 // Every output element has one producer and one summation order: no atomics, no scratch, the same bits on every call.
 //
+// BERT4Rec (reference model/sequential/BERT4Rec.py:123, attn_mask=None) takes the same kernels with the
+// CAUSAL flag off (srh_seq_attn_full_*): every wave walks all the key tiles below L, the columns >= L of the last tile are
+// masked before the row max (for a causal row they lie above the diagonal and need no test of their own), the dropout
+// multiplier is drawn for the whole row, and pass 2 sums over all the query tiles from 0, where rows >= L hold zeros.
+//
 // Dropout on P: keep[b][h][row][col] injected as bytes, or drawn from the counter RNG of common.h at counter
 // rng_counter + (b H + h) L + row, float4 number col / 4, word col % 4 (keep = u01(word) >= p); the backward redraws it.
 //
@@ -99,15 +104,26 @@ __device__ __forceinline__ float row_max4(float v) {
   return v;
 }
 
-// st[t][reg] = S[query 16 wave + j16][key 16t + 4g + reg] for the tiles t <= wave; qf: the lane's scaled query operand
-template <int DH>
-__device__ __forceinline__ void scores(const float* Ks, const float (&qf)[DH / 4], const int wave, const int g,
+// the key tiles a wave walks: up to its own when causal, every tile that holds a key otherwise
+template <bool CAUSAL>
+__device__ __forceinline__ bool walks_tile(const int t, const int wave, const int L) {
+  return CAUSAL ? t <= wave : 16 * t < L;
+}
+// the keys a query row attends to
+template <bool CAUSAL>
+__device__ __forceinline__ bool sees_key(const int col, const int row, const int L) {
+  return CAUSAL ? col <= row : col < L;
+}
+
+// st[t][reg] = S[query 16 wave + j16][key 16t + 4g + reg] for the tiles walked; qf: the lane's scaled query operand
+template <int DH, bool CAUSAL>
+__device__ __forceinline__ void scores(const float* Ks, const float (&qf)[DH / 4], const int wave, const int L, const int g,
                                        const int j16, f32x4 (&st)[4]) {
   constexpr int LD = DH + 4;
 #pragma unroll
   for (int t = 0; t < 4; ++t) {
     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-    if (t <= wave) {
+    if (walks_tile<CAUSAL>(t, wave, L)) {
       const float* arow = &Ks[(16 * t + j16) * LD + g];
 #pragma unroll
       for (int k = 0; k < DH / 4; ++k) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(arow[4 * k], qf[k], acc, 0, 0, 0);
@@ -116,18 +132,18 @@ __device__ __forceinline__ void scores(const float* Ks, const float (&qf)[DH / 4
   }
 }
 
-// out[u][reg] = sum over the keys of tiles t <= wave of Xs[key][16u + 4g + reg] bt[key], for query j16: the
+// out[u][reg] = sum over the keys of the tiles walked of Xs[key][16u + 4g + reg] bt[key], for query j16: the
 // accumulator-shaped bt[t][reg] (key 16t + 4g + reg) is the B operand as it stands, Xs (keys x DH in LDS) gives the A
 // operand's row for that k order
-template <int DH>
-__device__ __forceinline__ void seam_product(const float* Xs, const f32x4 (&bt)[4], const int wave, const int g,
+template <int DH, bool CAUSAL>
+__device__ __forceinline__ void seam_product(const float* Xs, const f32x4 (&bt)[4], const int wave, const int L, const int g,
                                              const int j16, f32x4 (&out)[DH / 16]) {
   constexpr int LD = DH + 4;
 #pragma unroll
   for (int u = 0; u < DH / 16; ++u) out[u] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
   for (int t = 0; t < 4; ++t) {
-    if (t <= wave) {
+    if (walks_tile<CAUSAL>(t, wave, L)) {
 #pragma unroll
       for (int reg = 0; reg < 4; ++reg) {
         const float* arow = &Xs[(16 * t + 4 * g + reg) * LD + j16];
@@ -140,7 +156,7 @@ __device__ __forceinline__ void seam_product(const float* Xs, const f32x4 (&bt)[
 }
 
 // ---- forward -----------------------------------------------------------------------------------------------------------
-template <int DH>
+template <int DH, bool CAUSAL>
 __global__ __launch_bounds__(256) void attn_fwd(AttnArgs a) {
   constexpr int LD = DH + 4;
   __shared__ float Ks[kMaxL * LD];
@@ -161,22 +177,22 @@ __global__ __launch_bounds__(256) void attn_fwd(AttnArgs a) {
 #pragma unroll
   for (int k = 0; k < DH / 4; ++k) qf[k] = rok ? a.q[base + (int64_t)row * E + 4 * k + g] * a.qscale : 0.f;
   f32x4 st[4];
-  scores<DH>(Ks, qf, wave, g, j16, st);
+  scores<DH, CAUSAL>(Ks, qf, wave, L, g, j16, st);
 
-  // causal mask and softmax of the row (key 0 <= row always: no empty row)
+  // the mask and the softmax of the row (key 0 is seen by every row: no empty row)
   float mx = -INFINITY;
 #pragma unroll
   for (int t = 0; t < 4; ++t)
 #pragma unroll
     for (int reg = 0; reg < 4; ++reg)
-      if (16 * t + 4 * g + reg <= row) mx = fmaxf(mx, st[t][reg]);
+      if (sees_key<CAUSAL>(16 * t + 4 * g + reg, row, L)) mx = fmaxf(mx, st[t][reg]);
   mx = row_max4(mx);
   float sum = 0.f;
 #pragma unroll
   for (int t = 0; t < 4; ++t)
 #pragma unroll
     for (int reg = 0; reg < 4; ++reg) {
-      const float p = (16 * t + 4 * g + reg <= row) ? expf(st[t][reg] - mx) : 0.f;
+      const float p = sees_key<CAUSAL>(16 * t + 4 * g + reg, row, L) ? expf(st[t][reg] - mx) : 0.f;
       st[t][reg] = p;
       sum += p;
     }
@@ -185,13 +201,13 @@ __global__ __launch_bounds__(256) void attn_fwd(AttnArgs a) {
 #pragma unroll
   for (int t = 0; t < 4; ++t) {
     float m[4] = {1.f, 1.f, 1.f, 1.f};
-    if (rok && t <= wave) drop_mult4(a, bh, row, t, g, m);
+    if (rok && walks_tile<CAUSAL>(t, wave, L)) drop_mult4(a, bh, row, t, g, m);
 #pragma unroll
     for (int reg = 0; reg < 4; ++reg) st[t][reg] = rok ? st[t][reg] * inv * m[reg] : 0.f;
   }
 
   f32x4 ot[DH / 16];
-  seam_product<DH>(Vs, st, wave, g, j16, ot);
+  seam_product<DH, CAUSAL>(Vs, st, wave, L, g, j16, ot);
   if (!rok) return;
 #pragma unroll
   for (int u = 0; u < DH / 16; ++u)
@@ -201,14 +217,15 @@ __global__ __launch_bounds__(256) void attn_fwd(AttnArgs a) {
 }
 
 // ---- backward ----------------------------------------------------------------------------------------------------------
-// dX[key 16 wave + j16][dim] = sum over queries of Xs[query][key] Ys[query][dim], query tiles wave .. nT - 1 ascending
-template <int DH>
+// dX[key 16 wave + j16][dim] = sum over queries of Xs[query][key] Ys[query][dim], query tiles (causal: wave, else 0) ..
+// nT - 1 ascending
+template <int DH, bool CAUSAL>
 __device__ __forceinline__ void key_tile_product(const float* Xs, const float* Ys, const int wave, const int nT, const int g,
                                                  const int j16, f32x4 (&out)[DH / 16]) {
   constexpr int LD = DH + 4;
 #pragma unroll
   for (int u = 0; u < DH / 16; ++u) out[u] = f32x4{0.f, 0.f, 0.f, 0.f};
-  for (int tq = wave; tq < nT; ++tq) {
+  for (int tq = CAUSAL ? wave : 0; tq < nT; ++tq) {
 #pragma unroll
     for (int kk = 0; kk < 4; ++kk) {
       const int qr = 16 * tq + 4 * kk + g;
@@ -220,7 +237,7 @@ __device__ __forceinline__ void key_tile_product(const float* Xs, const float* Y
   }
 }
 
-template <int DH>
+template <int DH, bool CAUSAL>
 __global__ __launch_bounds__(256) void attn_bwd(AttnArgs a) {
   constexpr int LD = DH + 4;
   __shared__ float Ks[kMaxL * LD];     // K, then Q
@@ -250,18 +267,18 @@ __global__ __launch_bounds__(256) void attn_bwd(AttnArgs a) {
       gof[k] = rok ? a.go[base + (int64_t)row * E + 4 * k + g] : 0.f;
     }
     f32x4 st[4];
-    scores<DH>(Ks, qf, wave, g, j16, st);
-    scores<DH>(Vs, gof, wave, g, j16, ds);     // ds[t][reg] = dP~[row][key 16t + 4g + reg] for now
+    scores<DH, CAUSAL>(Ks, qf, wave, L, g, j16, st);
+    scores<DH, CAUSAL>(Vs, gof, wave, L, g, j16, ds);     // ds[t][reg] = dP~[row][key 16t + 4g + reg] for now
     const float lse = rok ? a.lse_in[bh * L + row] : 0.f;
     float delta = 0.f;
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
       float m[4] = {1.f, 1.f, 1.f, 1.f};
-      if (rok && t <= wave) drop_mult4(a, bh, row, t, g, m);
+      if (rok && walks_tile<CAUSAL>(t, wave, L)) drop_mult4(a, bh, row, t, g, m);
 #pragma unroll
       for (int reg = 0; reg < 4; ++reg) {
 #pragma clang fp contract(off)    // dp is rounded before dp - delta: fused into it, a row whose dS is 0 (L = 1) keeps dust
-        const float p = (rok && 16 * t + 4 * g + reg <= row) ? expf(st[t][reg] - lse) : 0.f;
+        const float p = (rok && sees_key<CAUSAL>(16 * t + 4 * g + reg, row, L)) ? expf(st[t][reg] - lse) : 0.f;
         const float dp = ds[t][reg] * m[reg];
         st[t][reg] = p;
         ds[t][reg] = dp;
@@ -278,7 +295,7 @@ __global__ __launch_bounds__(256) void attn_bwd(AttnArgs a) {
         ds[t][reg] = st[t][reg] * (ds[t][reg] - delta) * a.qscale;
       }
     f32x4 gq[DH / 16];
-    seam_product<DH>(Ks, ds, wave, g, j16, gq);
+    seam_product<DH, CAUSAL>(Ks, ds, wave, L, g, j16, gq);
     if (rok) {
 #pragma unroll
       for (int u = 0; u < DH / 16; ++u)
@@ -292,14 +309,14 @@ __global__ __launch_bounds__(256) void attn_bwd(AttnArgs a) {
   if (active) {
 #pragma unroll
     for (int t = 0; t < 4; ++t)
-      if (t <= wave)
+      if (walks_tile<CAUSAL>(t, wave, L))
         *reinterpret_cast<float4*>(&Xs[row * kLdX + 16 * t + 4 * g]) = make_float4(pt[t][0], pt[t][1], pt[t][2], pt[t][3]);
   }
   __syncthreads();
   const int key = 16 * wave + j16;
   f32x4 acc[DH / 16];
   if (active) {
-    key_tile_product<DH>(Xs, Vs, wave, nT, g, j16, acc);     // dV = P~^T dO
+    key_tile_product<DH, CAUSAL>(Xs, Vs, wave, nT, g, j16, acc);     // dV = P~^T dO
     if (key < L) {
 #pragma unroll
       for (int u = 0; u < DH / 16; ++u)
@@ -311,12 +328,12 @@ __global__ __launch_bounds__(256) void attn_bwd(AttnArgs a) {
   if (active) {
 #pragma unroll
     for (int t = 0; t < 4; ++t)
-      if (t <= wave)
+      if (walks_tile<CAUSAL>(t, wave, L))
         *reinterpret_cast<float4*>(&Xs[row * kLdX + 16 * t + 4 * g]) = make_float4(ds[t][0], ds[t][1], ds[t][2], ds[t][3]);
   }
   __syncthreads();
   if (active) {
-    key_tile_product<DH>(Xs, Ks, wave, nT, g, j16, acc);     // dK = dS^T Q  (dS carries 1 / sqrt(dh))
+    key_tile_product<DH, CAUSAL>(Xs, Ks, wave, nT, g, j16, acc);     // dK = dS^T Q  (dS carries 1 / sqrt(dh))
     if (key < L) {
 #pragma unroll
       for (int u = 0; u < DH / 16; ++u)
@@ -396,6 +413,41 @@ __global__ __launch_bounds__(256) void bce_reduce(const double* __restrict__ ter
   if (threadIdx.x == 0) { loss[0] = sp[0] * inv_n; loss[1] = sn[0] * inv_n; }
 }
 
+template <bool CAUSAL>
+srh_status_t attn_fwd_launch(const char* what, const float* d_q, const float* d_k, const float* d_v, int64_t B, int32_t L,
+                             int32_t H, int32_t dh, const uint8_t* d_keep, uint64_t rng_seed, uint64_t rng_counter,
+                             float drop_p, float* d_out, float* d_lse, void* stream) {
+  SRH_REQUIRE(d_q && d_k && d_v && d_out && d_lse, "%s: null argument", what);
+  AttnArgs a{};
+  const srh_status_t s = attn_check(what, B, L, H, dh, d_keep, drop_p, a);
+  if (s != SRH_OK) return s;
+  a.q = d_q; a.k = d_k; a.v = d_v; a.out = d_out; a.lse = d_lse;
+  a.seed_lo = (uint32_t)rng_seed; a.seed_hi = (uint32_t)(rng_seed >> 32); a.ctr = rng_counter;
+  const unsigned grid = (unsigned)(B * H);
+  if (dh == 64) attn_fwd<64, CAUSAL><<<grid, 256, 0, as_stream(stream)>>>(a);
+  else attn_fwd<32, CAUSAL><<<grid, 256, 0, as_stream(stream)>>>(a);
+  SRH_LAUNCH_CHECK();
+  return SRH_OK;
+}
+
+template <bool CAUSAL>
+srh_status_t attn_bwd_launch(const char* what, const float* d_q, const float* d_k, const float* d_v, const float* d_go,
+                             const float* d_lse, int64_t B, int32_t L, int32_t H, int32_t dh, const uint8_t* d_keep,
+                             uint64_t rng_seed, uint64_t rng_counter, float drop_p, float* d_gq, float* d_gk, float* d_gv,
+                             void* stream) {
+  SRH_REQUIRE(d_q && d_k && d_v && d_go && d_lse && d_gq && d_gk && d_gv, "%s: null argument", what);
+  AttnArgs a{};
+  const srh_status_t s = attn_check(what, B, L, H, dh, d_keep, drop_p, a);
+  if (s != SRH_OK) return s;
+  a.q = d_q; a.k = d_k; a.v = d_v; a.go = d_go; a.lse_in = d_lse; a.gq = d_gq; a.gk = d_gk; a.gv = d_gv;
+  a.seed_lo = (uint32_t)rng_seed; a.seed_hi = (uint32_t)(rng_seed >> 32); a.ctr = rng_counter;
+  const unsigned grid = (unsigned)(B * H);
+  if (dh == 64) attn_bwd<64, CAUSAL><<<grid, 256, 0, as_stream(stream)>>>(a);
+  else attn_bwd<32, CAUSAL><<<grid, 256, 0, as_stream(stream)>>>(a);
+  SRH_LAUNCH_CHECK();
+  return SRH_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -403,34 +455,31 @@ extern "C" {
 srh_status_t srh_seq_attn_fwd_f32(const float* d_q, const float* d_k, const float* d_v, int64_t B, int32_t L, int32_t H,
                                   int32_t dh, const uint8_t* d_keep, uint64_t rng_seed, uint64_t rng_counter, float drop_p,
                                   float* d_out, float* d_lse, void* stream) {
-  SRH_REQUIRE(d_q && d_k && d_v && d_out && d_lse, "seq_attn_fwd: null argument");
-  AttnArgs a{};
-  const srh_status_t s = attn_check("seq_attn_fwd", B, L, H, dh, d_keep, drop_p, a);
-  if (s != SRH_OK) return s;
-  a.q = d_q; a.k = d_k; a.v = d_v; a.out = d_out; a.lse = d_lse;
-  a.seed_lo = (uint32_t)rng_seed; a.seed_hi = (uint32_t)(rng_seed >> 32); a.ctr = rng_counter;
-  const unsigned grid = (unsigned)(B * H);
-  if (dh == 64) attn_fwd<64><<<grid, 256, 0, as_stream(stream)>>>(a);
-  else attn_fwd<32><<<grid, 256, 0, as_stream(stream)>>>(a);
-  SRH_LAUNCH_CHECK();
-  return SRH_OK;
+  return attn_fwd_launch<true>("seq_attn_fwd", d_q, d_k, d_v, B, L, H, dh, d_keep, rng_seed, rng_counter, drop_p, d_out,
+                               d_lse, stream);
 }
 
 srh_status_t srh_seq_attn_bwd_f32(const float* d_q, const float* d_k, const float* d_v, const float* d_go,
                                   const float* d_lse, int64_t B, int32_t L, int32_t H, int32_t dh, const uint8_t* d_keep,
                                   uint64_t rng_seed, uint64_t rng_counter, float drop_p, float* d_gq, float* d_gk,
                                   float* d_gv, void* stream) {
-  SRH_REQUIRE(d_q && d_k && d_v && d_go && d_lse && d_gq && d_gk && d_gv, "seq_attn_bwd: null argument");
-  AttnArgs a{};
-  const srh_status_t s = attn_check("seq_attn_bwd", B, L, H, dh, d_keep, drop_p, a);
-  if (s != SRH_OK) return s;
-  a.q = d_q; a.k = d_k; a.v = d_v; a.go = d_go; a.lse_in = d_lse; a.gq = d_gq; a.gk = d_gk; a.gv = d_gv;
-  a.seed_lo = (uint32_t)rng_seed; a.seed_hi = (uint32_t)(rng_seed >> 32); a.ctr = rng_counter;
-  const unsigned grid = (unsigned)(B * H);
-  if (dh == 64) attn_bwd<64><<<grid, 256, 0, as_stream(stream)>>>(a);
-  else attn_bwd<32><<<grid, 256, 0, as_stream(stream)>>>(a);
-  SRH_LAUNCH_CHECK();
-  return SRH_OK;
+  return attn_bwd_launch<true>("seq_attn_bwd", d_q, d_k, d_v, d_go, d_lse, B, L, H, dh, d_keep, rng_seed, rng_counter,
+                               drop_p, d_gq, d_gk, d_gv, stream);
+}
+
+srh_status_t srh_seq_attn_full_fwd_f32(const float* d_q, const float* d_k, const float* d_v, int64_t B, int32_t L,
+                                       int32_t H, int32_t dh, const uint8_t* d_keep, uint64_t rng_seed,
+                                       uint64_t rng_counter, float drop_p, float* d_out, float* d_lse, void* stream) {
+  return attn_fwd_launch<false>("seq_attn_full_fwd", d_q, d_k, d_v, B, L, H, dh, d_keep, rng_seed, rng_counter, drop_p,
+                                d_out, d_lse, stream);
+}
+
+srh_status_t srh_seq_attn_full_bwd_f32(const float* d_q, const float* d_k, const float* d_v, const float* d_go,
+                                       const float* d_lse, int64_t B, int32_t L, int32_t H, int32_t dh,
+                                       const uint8_t* d_keep, uint64_t rng_seed, uint64_t rng_counter, float drop_p,
+                                       float* d_gq, float* d_gk, float* d_gv, void* stream) {
+  return attn_bwd_launch<false>("seq_attn_full_bwd", d_q, d_k, d_v, d_go, d_lse, B, L, H, dh, d_keep, rng_seed,
+                                rng_counter, drop_p, d_gq, d_gk, d_gv, stream);
 }
 
 int64_t srh_seq_bce_ws_bytes(int64_t R) { return R > 0 ? align256(16 * R) : 0; }

@@ -41,14 +41,16 @@ def attention_route(conf=None):
     return route
 
 
-def torch_causal_attention(q, k, v, n_heads, keep=None, drop_p=0.0, training=False):
-    """torch's expression of the attention core on projected (B, L, H dh) tensors: the partner of ops.SeqAttnFn"""
+def torch_causal_attention(q, k, v, n_heads, keep=None, drop_p=0.0, training=False, causal=True):
+    """torch's expression of the attention core on projected (B, L, H dh) tensors: the partner of ops.SeqAttnFn, and
+    with causal=False (no mask at all: BERT4Rec) of ops.SeqAttnFullFn"""
     B, L, E = q.shape
     dh = E // n_heads
     qh, kh, vh = (t.reshape(B, L, n_heads, dh).transpose(1, 2) for t in (q, k, v))
     s = torch.matmul(qh * (1.0 / math.sqrt(dh)), kh.transpose(-1, -2))
-    causal = torch.ones((L, L), dtype=torch.bool, device=q.device).tril()
-    p = torch.softmax(s.masked_fill(~causal, float('-inf')), dim=-1)
+    if causal:
+        s = s.masked_fill(~torch.ones((L, L), dtype=torch.bool, device=q.device).tril(), float('-inf'))
+    p = torch.softmax(s, dim=-1)
     if keep is not None:
         p = p * (keep.to(p.dtype) / (1.0 - drop_p))
     elif drop_p > 0.0:

@@ -27,7 +27,8 @@ __all__ = ["Sampler", "DeviceCSR", "column_class_order", "spmm", "spmm_any", "pa
            "find_k_largest_host_f64", "knn_neighbours", "knn_score_ws", "knn_score_topk",
            "tower_fwd", "tower_bwd", "scatter_plan", "scatter_plan_host", "rows_segment_sum", "batch_softmax_fwd_bwd", "TowerFn",
            "BatchSoftmaxFn", "seq_attn_supported", "seq_attn_fwd", "seq_attn_bwd", "SeqAttnFn", "seq_bce_fwd_bwd", "SeqBceFn",
-           "GatherRowsFn", "SelfrecHipError"]
+           "GatherRowsFn", "seq_attn_full_fwd", "seq_attn_full_bwd", "SeqAttnFullFn", "table_ce_fwd_bwd", "TableCeFn",
+           "SelfrecHipError"]
 
 
 def _stream() -> int:
@@ -1462,33 +1463,52 @@ def _attn_keep(keep, B, H, L):
     return keep.to(torch.uint8).contiguous()
 
 
-def seq_attn_fwd(q, k, v, n_heads, *, keep=None, drop_p=0.0, rng_seed=0, rng_counter=0):
-    """Causal attention of projected q, k, v (B, L, H * dh): (out (B, L, H * dh), lse (B, H, L)).  Dropout on the
-    probabilities: ``keep`` ((B, H, L, L), 1 = keep) replays a given mask; without it and with drop_p > 0 the mask is
-    drawn in-kernel at the counters [rng_counter, rng_counter + B * H * L) (include/selfrec_hip.h)."""
+def _seq_attn_fwd(entry, q, k, v, n_heads, keep, drop_p, rng_seed, rng_counter):
     B, L, H, dh = _attn_shape(q, k, v, n_heads)
     keep = _attn_keep(keep, B, H, L)
     out = torch.empty_like(q)
     lse = torch.empty((B, H, L), dtype=torch.float32, device=q.device)
-    check(_lib.load().srh_seq_attn_fwd_f32(_p(q, torch.float32, "q"), _p(k, torch.float32, "k"), _p(v, torch.float32, "v"),
-                                           B, L, H, dh, _p(keep, torch.uint8, "keep"),
-                                           int(rng_seed) & 0xFFFFFFFFFFFFFFFF, int(rng_counter) & 0xFFFFFFFFFFFFFFFF,
-                                           float(drop_p), _p(out), _p(lse), _stream()), "srh_seq_attn_fwd_f32")
+    check(getattr(_lib.load(), entry)(_p(q, torch.float32, "q"), _p(k, torch.float32, "k"), _p(v, torch.float32, "v"),
+                                      B, L, H, dh, _p(keep, torch.uint8, "keep"),
+                                      int(rng_seed) & 0xFFFFFFFFFFFFFFFF, int(rng_counter) & 0xFFFFFFFFFFFFFFFF,
+                                      float(drop_p), _p(out), _p(lse), _stream()), entry)
     return out, lse
 
 
-def seq_attn_bwd(q, k, v, lse, go, n_heads, *, keep=None, drop_p=0.0, rng_seed=0, rng_counter=0):
-    """(dq, dk, dv) of seq_attn_fwd for the upstream gradient go, with the forward's dropout arguments."""
+def _seq_attn_bwd(entry, q, k, v, lse, go, n_heads, keep, drop_p, rng_seed, rng_counter):
     B, L, H, dh = _attn_shape(q, k, v, n_heads)
     keep = _attn_keep(keep, B, H, L)
     go = go.to(torch.float32).contiguous()
     gq, gk, gv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
-    check(_lib.load().srh_seq_attn_bwd_f32(_p(q, torch.float32, "q"), _p(k, torch.float32, "k"), _p(v, torch.float32, "v"),
-                                           _p(go, torch.float32, "go"), _p(lse, torch.float32, "lse"), B, L, H, dh,
-                                           _p(keep, torch.uint8, "keep"), int(rng_seed) & 0xFFFFFFFFFFFFFFFF,
-                                           int(rng_counter) & 0xFFFFFFFFFFFFFFFF, float(drop_p), _p(gq), _p(gk), _p(gv),
-                                           _stream()), "srh_seq_attn_bwd_f32")
+    check(getattr(_lib.load(), entry)(_p(q, torch.float32, "q"), _p(k, torch.float32, "k"), _p(v, torch.float32, "v"),
+                                      _p(go, torch.float32, "go"), _p(lse, torch.float32, "lse"), B, L, H, dh,
+                                      _p(keep, torch.uint8, "keep"), int(rng_seed) & 0xFFFFFFFFFFFFFFFF,
+                                      int(rng_counter) & 0xFFFFFFFFFFFFFFFF, float(drop_p), _p(gq), _p(gk), _p(gv),
+                                      _stream()), entry)
     return gq, gk, gv
+
+
+def seq_attn_fwd(q, k, v, n_heads, *, keep=None, drop_p=0.0, rng_seed=0, rng_counter=0):
+    """Causal attention of projected q, k, v (B, L, H * dh): (out (B, L, H * dh), lse (B, H, L)).  Dropout on the
+    probabilities: ``keep`` ((B, H, L, L), 1 = keep) replays a given mask; without it and with drop_p > 0 the mask is
+    drawn in-kernel at the counters [rng_counter, rng_counter + B * H * L) (include/selfrec_hip.h)."""
+    return _seq_attn_fwd("srh_seq_attn_fwd_f32", q, k, v, n_heads, keep, drop_p, rng_seed, rng_counter)
+
+
+def seq_attn_bwd(q, k, v, lse, go, n_heads, *, keep=None, drop_p=0.0, rng_seed=0, rng_counter=0):
+    """(dq, dk, dv) of seq_attn_fwd for the upstream gradient go, with the forward's dropout arguments."""
+    return _seq_attn_bwd("srh_seq_attn_bwd_f32", q, k, v, lse, go, n_heads, keep, drop_p, rng_seed, rng_counter)
+
+
+def seq_attn_full_fwd(q, k, v, n_heads, *, keep=None, drop_p=0.0, rng_seed=0, rng_counter=0):
+    """seq_attn_fwd without a mask: every query attends to all L positions (BERT4Rec).  The same arguments, outputs
+    and dropout contract."""
+    return _seq_attn_fwd("srh_seq_attn_full_fwd_f32", q, k, v, n_heads, keep, drop_p, rng_seed, rng_counter)
+
+
+def seq_attn_full_bwd(q, k, v, lse, go, n_heads, *, keep=None, drop_p=0.0, rng_seed=0, rng_counter=0):
+    """(dq, dk, dv) of seq_attn_full_fwd for the upstream gradient go, with the forward's dropout arguments."""
+    return _seq_attn_bwd("srh_seq_attn_full_bwd_f32", q, k, v, lse, go, n_heads, keep, drop_p, rng_seed, rng_counter)
 
 
 class SeqAttnFn(torch.autograd.Function):
@@ -1508,6 +1528,27 @@ class SeqAttnFn(torch.autograd.Function):
         n_heads, keep, drop_p, rng_seed, rng_counter = ctx.args
         gq, gk, gv = seq_attn_bwd(q, k, v, lse, go, n_heads, keep=keep, drop_p=drop_p, rng_seed=rng_seed,
                                   rng_counter=rng_counter)
+        return gq, gk, gv, None, None, None, None, None
+
+
+class SeqAttnFullFn(torch.autograd.Function):
+    """seq_attn_full_fwd / seq_attn_full_bwd as one differentiable op of (q, k, v)."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, n_heads, keep, drop_p, rng_seed, rng_counter):
+        q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
+        out, lse = seq_attn_full_fwd(q, k, v, n_heads, keep=keep, drop_p=drop_p, rng_seed=rng_seed,
+                                     rng_counter=rng_counter)
+        ctx.save_for_backward(q, k, v, lse)
+        ctx.args = (n_heads, keep, drop_p, rng_seed, rng_counter)
+        return out
+
+    @staticmethod
+    def backward(ctx, go):
+        q, k, v, lse = ctx.saved_tensors
+        n_heads, keep, drop_p, rng_seed, rng_counter = ctx.args
+        gq, gk, gv = seq_attn_full_bwd(q, k, v, lse, go, n_heads, keep=keep, drop_p=drop_p, rng_seed=rng_seed,
+                                       rng_counter=rng_counter)
         return gq, gk, gv, None, None, None, None, None
 
 
@@ -1568,3 +1609,49 @@ class GatherRowsFn(torch.autograd.Function):
     def backward(ctx, g):
         g2 = g.reshape(-1, ctx.table_shape[1]).to(torch.float32).contiguous()
         return rows_segment_sum(g2, ctx.plan, torch.zeros(ctx.table_shape, dtype=torch.float32, device=g.device)), None, None
+
+
+# ---- BERT4Rec (csrc/contrastive.hip: the table cross-entropy) -------------------------------------------------------------
+def table_ce_fwd_bwd(hidden_rows, table, labels, loss_scale=1.0, ws=None):
+    """Softmax cross-entropy of the rows (M x d) against the whole table (N x d), logits h_m . t_j:
+    (loss (0-dim float64) = loss_scale * sum_m (lse_m - s_{m, label_m}), dL/dhidden_rows (M x d), dL/dtable (N x d, dense)).
+    labels: int32 device tensor of M entries in [0, N).  The M x N logits are never materialised.  Rows up to 128 columns
+    (narrower ones zero-padded: no result changes)."""
+    if hidden_rows.dim() != 2 or table.dim() != 2 or hidden_rows.shape[1] != table.shape[1]:
+        raise SelfrecHipError("table_ce: rows (M x d) and table (N x d) expected")
+    M, d = int(hidden_rows.shape[0]), int(hidden_rows.shape[1])
+    N = int(table.shape[0])
+    if int(labels.numel()) != M:
+        raise SelfrecHipError(f"table_ce: labels has {int(labels.numel())} entries, expected {M}")
+    w = padded_width(d, TABLE_NCE_WIDTHS)
+    if w is None:
+        raise SelfrecHipError(f"table_ce: rows of {d} columns -- the kernel serves up to {TABLE_NCE_WIDTHS[-1]}")
+    _p(hidden_rows, None, "hidden_rows"), _p(table, None, "table")
+    hp, tp = pad_cols(hidden_rows.float(), w).contiguous(), pad_cols(table.float(), w).contiguous()
+    dev = hidden_rows.device
+    need = int(_lib.load().srh_table_ce_ws_bytes(M, N, w))
+    if ws is None or ws.numel() * ws.element_size() < need:
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    loss = torch.empty((), dtype=torch.float64, device=dev)
+    gh = torch.empty((M, w), dtype=torch.float32, device=dev)
+    gt = torch.empty((N, w), dtype=torch.float32, device=dev)
+    check(_lib.load().srh_table_ce_fwd_bwd(_p(hp, torch.float32, "hidden_rows"), M, _p(tp, torch.float32, "table"), N, w,
+                                           _p(labels, torch.int32, "labels"), float(loss_scale), _p(loss), _p(gh), _p(gt),
+                                           _p(ws), _stream()), "srh_table_ce_fwd_bwd")
+    return loss, (gh if w == d else gh[:, :d]), (gt if w == d else gt[:, :d])
+
+
+class TableCeFn(torch.autograd.Function):
+    """table_ce_fwd_bwd as one differentiable op of (hidden_rows, table): loss and both gradients come out of the one
+    call; backward() scales them by the upstream scalar."""
+
+    @staticmethod
+    def forward(ctx, hidden_rows, table, labels, loss_scale):
+        loss, gh, gt = table_ce_fwd_bwd(hidden_rows, table, labels, loss_scale)
+        ctx.save_for_backward(gh, gt)
+        return loss.to(torch.float32)
+
+    @staticmethod
+    def backward(ctx, gout):
+        gh, gt = ctx.saved_tensors
+        return gh * gout, gt * gout, None, None
