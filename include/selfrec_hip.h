@@ -918,6 +918,66 @@ srh_status_t srh_table_ce_fwd_bwd(const float* d_h, int64_t M, const float* d_t,
                                   void* d_ws, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * (a-18) CL4SRec -- the embedding front of SASRec_Model.forward (model/sequential/SASRec.py:70-76: both gathers, the
+ * scale, the sum, nn.Dropout, the padding mask) as model/sequential/CL4SRec.py:36-55 calls it three times a step, and the
+ * table gradients behind it and behind calculate_loss.
+ *
+ * srh_seq_embed_fwd_f32: for the R rows of ids d_seq / d_posid (int32): a LIVE row (seq[r] != 0) gets
+ *     out[r][c] = (item[seq[r]][c] * scale + pos[posid[r]][c]) * m(r, c)
+ *   with the product and the sum rounded separately (no fma: at drop_p = 0 the bits of torch's items * scale + places).
+ *   Every other row gets exact zeros and no table row is read for it (row 0 of either table is an ordinary initialised
+ *   row).  An id outside its table (seq[r] < 0 or >= n_item, posid[r] < 0 or >= n_pos) makes a zero row, as in
+ *   srh_tower_fwd_f32.  m = keep ? 1 / (1 - drop_p) : 0;  keep[r][c] is d_keep[r * d + c] != 0 when d_keep is given, else
+ *   (drop_p > 0) drawn under the tower's contract: the word c % 4 of float4 c / 4 at counter rng_counter + r,
+ *   keep = u01(word) >= drop_p -- a pure function of (seed, counter, r, c).  One call uses the counters
+ *   [rng_counter, rng_counter + R).  d = 32, 64 or 128 (else SRH_ERR_UNSUPPORTED), any R >= 1.
+ * srh_rows_live_sum_f32: up to SRH_LIVE_SUM_MAX_PROBLEMS deterministic segment sums in one pair of launches.  A problem's
+ *   plan (ops.live_plan_host) lists the rows of d_x (n_rows x d) that matter, sorted stably by their table row:
+ *     d_rows (n_live)              the listed rows, segment after segment
+ *     d_chunk_start (n_chunk + 1)  every segment cut into chunks of at most SRH_LIVE_SUM_CHUNK entries of d_rows
+ *     d_chunk_dst (n_chunk)        the table row when the chunk is its segment's only one, else -1
+ *     d_multi_range (2 n_multi)    first chunk and one past the last chunk of every segment of two chunks or more
+ *     d_multi_row (n_multi)        those segments' table rows
+ *   and  d_out[row] = scale * sum over the segment's rows r, in plan order, of x[r] * m(r)  is WRITTEN for every table
+ *   row the plan names; rows it does not name are left as they were (the caller zero-fills), rows of d_x it does not list
+ *   are never read.  Launch 1: one lane group per chunk; the only chunk of a segment writes the table row, the others a
+ *   partial to d_ws.  Launch 2 (when a problem has a cut segment): one lane group per such segment adds its partials in
+ *   chunk order.  No float atomics: one producer and one order per output element, the same bits on every call.  m is the
+ *   forward's dropout multiplier of row r (d_keep of n_rows x d bytes, or drawn at rng_counter + r when drop_p > 0, or
+ *   1), so a backward pass redraws it instead of storing it.  A problem with n_chunk == 0 writes nothing; d, the widths of
+ *   srh_seq_embed_fwd_f32, is shared by the problems of a call.  `problems` is a HOST array;
+ *   d_ws >= srh_rows_live_sum_ws_bytes(problems, n_problems, d) (0 when no segment is cut).
+ * ---------------------------------------------------------------------------------- */
+#define SRH_LIVE_SUM_CHUNK 32
+#define SRH_LIVE_SUM_MAX_PROBLEMS 3
+srh_status_t srh_seq_embed_fwd_f32(const float* d_item, int64_t n_item, const float* d_pos, int64_t n_pos,
+                                   const int32_t* d_seq, const int32_t* d_posid, int64_t R, int32_t d, float scale,
+                                   const uint8_t* d_keep, uint64_t rng_seed, uint64_t rng_counter, float drop_p,
+                                   float* d_out, void* stream);
+typedef struct srh_live_sum_problem {
+  const float* d_x;
+  int64_t n_rows;
+  const int32_t* d_rows;
+  const int32_t* d_chunk_start;
+  const int32_t* d_chunk_dst;
+  const int32_t* d_multi_range;
+  const int32_t* d_multi_row;
+  int64_t n_live;
+  int64_t n_chunk;
+  int64_t n_multi;
+  float* d_out;
+  int64_t n_table;
+  float scale;
+  float drop_p;
+  const uint8_t* d_keep;
+  uint64_t rng_seed;
+  uint64_t rng_counter;
+} srh_live_sum_problem_t;
+int64_t srh_rows_live_sum_ws_bytes(const srh_live_sum_problem_t* problems, int32_t n_problems, int32_t d);
+srh_status_t srh_rows_live_sum_f32(const srh_live_sum_problem_t* problems, int32_t n_problems, int32_t d, void* d_ws,
+                                   void* stream);
+
+/* ------------------------------------------------------------------------------------
  * (f-1) Dataset files -> id arrays -- replaces the python loops of data/loader.py:22-33
  * (FileIO.load_data_set: one "user item weight" line per interaction, single-space separated)
  * and data/ui_graph.py:29-45 (ids in first-appearance order of the training file; test pairs kept

@@ -61,6 +61,15 @@ class TowerWeights(C.Structure):
     _fields_ = [("d_w1", C.c_void_p), ("d_b1", C.c_void_p), ("d_w2", C.c_void_p), ("d_b2", C.c_void_p)]
 
 
+class LiveSumProblem(C.Structure):
+    """struct srh_live_sum_problem (include/selfrec_hip.h)."""
+    _fields_ = [("d_x", C.c_void_p), ("n_rows", C.c_int64), ("d_rows", C.c_void_p), ("d_chunk_start", C.c_void_p),
+                ("d_chunk_dst", C.c_void_p), ("d_multi_range", C.c_void_p), ("d_multi_row", C.c_void_p),
+                ("n_live", C.c_int64), ("n_chunk", C.c_int64), ("n_multi", C.c_int64), ("d_out", C.c_void_p),
+                ("n_table", C.c_int64), ("scale", C.c_float), ("drop_p", C.c_float), ("d_keep", C.c_void_p),
+                ("rng_seed", C.c_uint64), ("rng_counter", C.c_uint64)]
+
+
 SCALAR_WS_BYTES = 64         # SRH_SCALAR_WS_BYTES
 
 
@@ -189,6 +198,9 @@ SIGNATURES = {
     "srh_table_ce_fwd_bwd": (_i32, [_vp, _i64, _vp, _i64, _i32, _vp, _f32, _vp, _vp, _vp, _vp, _vp]),
     "srh_seq_bce_ws_bytes": (_i64, [_i64]),
     "srh_seq_bce_fwd_bwd": (_i32, [_vp, _i64, _i32, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "srh_seq_embed_fwd_f32": (_i32, [_vp, _i64, _vp, _i64, _vp, _vp, _i64, _i32, _f32, _vp, _u64, _u64, _f32, _vp, _vp]),
+    "srh_rows_live_sum_ws_bytes": (_i64, [C.POINTER(LiveSumProblem), _i32, _i32]),
+    "srh_rows_live_sum_f32": (_i32, [C.POINTER(LiveSumProblem), _i32, _i32, _vp, _vp]),
     "srh_adam_step": (_i32, [_vp, _vp, _vp, _vp, _i64, _i64, _vp, _f32, _f32, _f32, _f32, _vp]),
     "srh_adam_step_reset": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _vp, _f32, _f32, _f32, _f32, _vp, _i32, _vp, _vp, _vp]),
     "srh_score_mask_topk": (_i32, [_vp, _vp, _i64, _vp, _i64, _i32, _vp, _vp, _i32, _vp, _i64, _vp, _vp, _vp]),

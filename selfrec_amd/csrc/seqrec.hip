@@ -28,6 +28,13 @@
 // srh_seq_bce_fwd_bwd: one wave per hidden row gathers the target and the negative item rows, forms both logits and
 // writes the row's two loss terms (float64), dL/dh and the two per-row table gradients; one workgroup then sums the
 // terms in a fixed order.  The table gradient itself is srh_rows_segment_sum_f32 over the per-row gradients.
+//
+// CL4SRec (reference model/sequential/CL4SRec.py) runs the encoder on three stacked views, most of whose rows
+// are padding.  srh_seq_embed_fwd_f32 is the embedding front in one launch: gather of both tables, scale, sum, dropout, and
+// exact zeros for the dead rows without reading a table row for them.  srh_rows_live_sum_f32 is the table gradient behind it
+// and behind the BCE: a segment sum over a host-built plan that lists live rows only and cuts every segment into chunks of
+// SRH_LIVE_SUM_CHUNK rows -- one lane group per chunk, a second launch that adds the partials of the cut segments in chunk
+// order; no atomics, one producer and one order per output element.
 #include "common.h"
 
 namespace {
@@ -413,6 +420,156 @@ __global__ __launch_bounds__(256) void bce_reduce(const double* __restrict__ ter
   if (threadIdx.x == 0) { loss[0] = sp[0] * inv_n; loss[1] = sn[0] * inv_n; }
 }
 
+// ---- CL4SRec: the embedding front and the live-row table gradient -------------------------------------
+// Dropout on the embedding rows: keep[r][c] injected as bytes, or drawn at counter rng_counter + r, float4 number c / 4,
+// word c % 4 (keep = u01(word) >= p) -- the tower's contract (ssl4rec.hip).  One lane owns one float4 of a row.
+struct RowDrop {
+  const uint8_t* keep;
+  int mode;
+  uint32_t seed_lo, seed_hi;
+  uint64_t ctr;
+  float p, scale;
+};
+
+__device__ __forceinline__ float4 row_drop_mult(const RowDrop& dr, const int64_t r, const int d, const int v) {
+  if (dr.mode == DROP_NONE) return make_float4(1.f, 1.f, 1.f, 1.f);
+  if (dr.mode == DROP_GIVEN) {
+    const uint8_t* kp = dr.keep + r * d + 4 * v;
+    return make_float4(kp[0] ? dr.scale : 0.f, kp[1] ? dr.scale : 0.f, kp[2] ? dr.scale : 0.f, kp[3] ? dr.scale : 0.f);
+  }
+  const uint4 w = counter_rng4(dr.ctr + (uint64_t)r, (uint32_t)v, dr.seed_lo, dr.seed_hi);
+  return make_float4(u01(w.x) >= dr.p ? dr.scale : 0.f, u01(w.y) >= dr.p ? dr.scale : 0.f,
+                     u01(w.z) >= dr.p ? dr.scale : 0.f, u01(w.w) >= dr.p ? dr.scale : 0.f);
+}
+
+inline RowDrop make_row_drop(const uint8_t* d_keep, uint64_t rng_seed, uint64_t rng_counter, float drop_p) {
+  RowDrop dr{};
+  dr.keep = d_keep;
+  dr.mode = d_keep ? DROP_GIVEN : (drop_p > 0.f ? DROP_DRAWN : DROP_NONE);
+  dr.seed_lo = (uint32_t)rng_seed; dr.seed_hi = (uint32_t)(rng_seed >> 32); dr.ctr = rng_counter;
+  dr.p = drop_p; dr.scale = 1.f / (1.f - drop_p);
+  return dr;
+}
+
+// out[r] = (item[seq[r]] * scale + pos[posid[r]]) * m(r) for the live rows (seq[r] != 0, both ids inside their tables),
+// exact zeros for every other row, whose table rows are not read.  d / 4 lanes per row.
+__global__ __launch_bounds__(256) void seq_embed_rows(const float* __restrict__ item, int64_t n_item,
+                                                      const float* __restrict__ pos, int64_t n_pos,
+                                                      const int32_t* __restrict__ seq, const int32_t* __restrict__ posid,
+                                                      int64_t R, int32_t d, float scale, RowDrop dr, float* __restrict__ out) {
+  const int lpr = d >> 2;
+  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int64_t r = t / lpr;
+  const int v = (int)(t % lpr);
+  if (r >= R) return;
+  const int64_t it = seq[r], pl = posid[r];
+  float4 o = f4_zero();
+  if (it > 0 && it < n_item && pl >= 0 && pl < n_pos) {
+    const float4 a = *reinterpret_cast<const float4*>(item + it * d + 4 * v);
+    const float4 b = *reinterpret_cast<const float4*>(pos + pl * d + 4 * v);
+    const float4 m = row_drop_mult(dr, r, d, v);
+    {
+#pragma clang fp contract(off)    // product, sum and mask rounded one by one: torch's items * sqrt(d) + places, bit for bit
+      const float4 s = make_float4(a.x * scale, a.y * scale, a.z * scale, a.w * scale);
+      const float4 e = make_float4(s.x + b.x, s.y + b.y, s.z + b.z, s.w + b.w);
+      o = make_float4(e.x * m.x, e.y * m.y, e.z * m.z, e.w * m.w);
+    }
+  }
+  *reinterpret_cast<float4*>(out + r * d + 4 * v) = o;
+}
+
+// One problem of srh_rows_live_sum_f32 as the kernels read it.
+struct LiveSumTask {
+  const float* x;
+  const int32_t *rows, *chunk_start, *chunk_dst, *multi_range, *multi_row;
+  float* out;
+  float* part;          // n_chunk x d partial sums (multi-chunk segments only)
+  int64_t n_x, n_live, n_chunk, n_multi, n_table;
+  float scale;
+  RowDrop dr;
+};
+struct LiveSumBatch {
+  LiveSumTask t[SRH_LIVE_SUM_MAX_PROBLEMS];
+  int64_t chunk_end[SRH_LIVE_SUM_MAX_PROBLEMS];   // running totals of n_chunk / n_multi: group g -> (problem, local index)
+  int64_t multi_end[SRH_LIVE_SUM_MAX_PROBLEMS];
+  int count;
+  int d;
+};
+
+__device__ __forceinline__ float4 f4_fma_mask(const float4 x, const float4 m, const float4 acc) {
+  return make_float4(fmaf(x.x, m.x, acc.x), fmaf(x.y, m.y, acc.y), fmaf(x.z, m.z, acc.z), fmaf(x.w, m.w, acc.w));
+}
+
+// launch 1: one group of d / 4 lanes per chunk sums the chunk's rows of x (times their dropout multiplier) in plan order.
+// The only chunk of a segment writes scale * sum to its table row; a chunk of a longer segment leaves its sum in part[].
+__global__ __launch_bounds__(256) void live_sum_chunks(const LiveSumBatch b) {
+  const int d = b.d, lpr = d >> 2;
+  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  int64_t g = t / lpr;
+  const int v = (int)(t % lpr);
+  int k = 0;
+  while (k < b.count && g >= b.chunk_end[k]) ++k;
+  if (k >= b.count) return;
+  if (k > 0) g -= b.chunk_end[k - 1];
+  const LiveSumTask& w = b.t[k];
+  int64_t p0 = w.chunk_start[g], p1 = w.chunk_start[g + 1];
+  p0 = p0 < 0 ? 0 : p0;
+  p1 = p1 > w.n_live ? w.n_live : p1;
+  float4 acc = f4_zero();
+  int64_t p = p0;
+  // four rows in flight: their ids, then their loads, then the adds in plan order
+  for (; p + 4 <= p1; p += 4) {
+    int64_t r[4];
+    float4 x[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) r[u] = w.rows[p + u];
+#pragma unroll
+    for (int u = 0; u < 4; ++u)
+      x[u] = (r[u] >= 0 && r[u] < w.n_x) ? *reinterpret_cast<const float4*>(w.x + r[u] * d + 4 * v) : f4_zero();
+#pragma unroll
+    for (int u = 0; u < 4; ++u)
+      if (r[u] >= 0 && r[u] < w.n_x) acc = f4_fma_mask(x[u], row_drop_mult(w.dr, r[u], d, v), acc);
+  }
+  for (; p < p1; ++p) {
+    const int64_t r = w.rows[p];
+    if (r >= 0 && r < w.n_x)
+      acc = f4_fma_mask(*reinterpret_cast<const float4*>(w.x + r * d + 4 * v), row_drop_mult(w.dr, r, d, v), acc);
+  }
+  const int64_t dst = w.chunk_dst[g];
+  if (dst >= 0) {
+    if (dst < w.n_table)
+      *reinterpret_cast<float4*>(w.out + dst * d + 4 * v) =
+          make_float4(w.scale * acc.x, w.scale * acc.y, w.scale * acc.z, w.scale * acc.w);
+  } else if (w.part) {
+    *reinterpret_cast<float4*>(w.part + g * d + 4 * v) = acc;
+  }
+}
+
+// launch 2: one group per multi-chunk segment adds its partials in chunk order
+__global__ __launch_bounds__(256) void live_sum_finish(const LiveSumBatch b) {
+  const int d = b.d, lpr = d >> 2;
+  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  int64_t g = t / lpr;
+  const int v = (int)(t % lpr);
+  int k = 0;
+  while (k < b.count && g >= b.multi_end[k]) ++k;
+  if (k >= b.count) return;
+  if (k > 0) g -= b.multi_end[k - 1];
+  const LiveSumTask& w = b.t[k];
+  int64_t c0 = w.multi_range[2 * g], c1 = w.multi_range[2 * g + 1];
+  c0 = c0 < 0 ? 0 : c0;
+  c1 = c1 > w.n_chunk ? w.n_chunk : c1;
+  float4 acc = f4_zero();
+  for (int64_t c = c0; c < c1; ++c) {
+    const float4 x = *reinterpret_cast<const float4*>(w.part + c * d + 4 * v);
+    acc = make_float4(acc.x + x.x, acc.y + x.y, acc.z + x.z, acc.w + x.w);
+  }
+  const int64_t dst = w.multi_row[g];
+  if (dst >= 0 && dst < w.n_table)
+    *reinterpret_cast<float4*>(w.out + dst * d + 4 * v) =
+        make_float4(w.scale * acc.x, w.scale * acc.y, w.scale * acc.z, w.scale * acc.w);
+}
+
 template <bool CAUSAL>
 srh_status_t attn_fwd_launch(const char* what, const float* d_q, const float* d_k, const float* d_v, int64_t B, int32_t L,
                              int32_t H, int32_t dh, const uint8_t* d_keep, uint64_t rng_seed, uint64_t rng_counter,
@@ -499,6 +656,76 @@ srh_status_t srh_seq_bce_fwd_bwd(const float* d_hidden, int64_t R, int32_t d, co
   SRH_LAUNCH_CHECK();
   bce_reduce<<<1, 256, 0, st>>>(terms, R, inv_n, d_loss2);
   SRH_LAUNCH_CHECK();
+  return SRH_OK;
+}
+
+srh_status_t srh_seq_embed_fwd_f32(const float* d_item, int64_t n_item, const float* d_pos, int64_t n_pos,
+                                   const int32_t* d_seq, const int32_t* d_posid, int64_t R, int32_t d, float scale,
+                                   const uint8_t* d_keep, uint64_t rng_seed, uint64_t rng_counter, float drop_p,
+                                   float* d_out, void* stream) {
+  SRH_REQUIRE(d_item && d_pos && d_seq && d_posid && d_out, "seq_embed_fwd: null argument");
+  SRH_REQUIRE(R >= 1 && R < (int64_t(1) << 31) && n_item >= 1 && n_pos >= 1, "seq_embed_fwd: bad sizes");
+  SRH_REQUIRE(drop_p >= 0.f && drop_p < 1.f, "seq_embed_fwd: drop probability must be in [0, 1)");
+  SRH_SUPPORTED(d == 32 || d == 64 || d == 128, "seq_embed_fwd: width %d -- the kernel serves 32, 64 and 128", d);
+  const RowDrop dr = make_row_drop(d_keep, rng_seed, rng_counter, drop_p);
+  const int64_t threads = R * (d / 4);
+  seq_embed_rows<<<(unsigned)((threads + 255) / 256), 256, 0, as_stream(stream)>>>(d_item, n_item, d_pos, n_pos, d_seq,
+                                                                                    d_posid, R, d, scale, dr, d_out);
+  SRH_LAUNCH_CHECK();
+  return SRH_OK;
+}
+
+int64_t srh_rows_live_sum_ws_bytes(const srh_live_sum_problem_t* problems, int32_t n_problems, int32_t d) {
+  int64_t need = 0;
+  for (int k = 0; problems && k < n_problems; ++k)
+    if (problems[k].n_multi > 0) need += align256(problems[k].n_chunk * d * (int64_t)sizeof(float));
+  return need;
+}
+
+srh_status_t srh_rows_live_sum_f32(const srh_live_sum_problem_t* problems, int32_t n_problems, int32_t d, void* d_ws,
+                                   void* stream) {
+  SRH_REQUIRE(problems && n_problems >= 1 && n_problems <= SRH_LIVE_SUM_MAX_PROBLEMS,
+              "rows_live_sum: 1..%d problems per call", SRH_LIVE_SUM_MAX_PROBLEMS);
+  SRH_SUPPORTED(d == 32 || d == 64 || d == 128, "rows_live_sum: width %d -- the kernel serves 32, 64 and 128", d);
+  LiveSumBatch b{};
+  b.d = d;
+  char* cursor = static_cast<char*>(d_ws);
+  int64_t chunks = 0, multis = 0;
+  for (int k = 0; k < n_problems; ++k) {
+    const srh_live_sum_problem_t& p = problems[k];
+    SRH_REQUIRE(p.n_rows >= 1 && p.n_rows < (int64_t(1) << 31) && p.n_table >= 1 && p.n_live >= 0 && p.n_live <= p.n_rows &&
+                    p.n_chunk >= 0 && p.n_chunk <= p.n_live && p.n_multi >= 0 && 2 * p.n_multi <= p.n_chunk,
+                "rows_live_sum: problem %d: bad sizes", k);
+    SRH_REQUIRE(p.drop_p >= 0.f && p.drop_p < 1.f, "rows_live_sum: drop probability must be in [0, 1)");
+    SRH_REQUIRE(p.n_chunk == 0 || (p.d_x && p.d_rows && p.d_chunk_start && p.d_chunk_dst && p.d_out),
+                "rows_live_sum: problem %d: null argument", k);
+    SRH_REQUIRE(p.n_multi == 0 || (p.d_multi_range && p.d_multi_row && d_ws),
+                "rows_live_sum: problem %d: multi-chunk segments without their lists or a workspace", k);
+    LiveSumTask& w = b.t[k];
+    w.x = p.d_x; w.rows = p.d_rows; w.chunk_start = p.d_chunk_start; w.chunk_dst = p.d_chunk_dst;
+    w.multi_range = p.d_multi_range; w.multi_row = p.d_multi_row; w.out = p.d_out;
+    w.n_x = p.n_rows; w.n_live = p.n_live; w.n_chunk = p.n_chunk; w.n_multi = p.n_multi; w.n_table = p.n_table;
+    w.scale = p.scale;
+    w.dr = make_row_drop(p.d_keep, p.rng_seed, p.rng_counter, p.drop_p);
+    w.part = nullptr;
+    if (p.n_multi > 0) {
+      w.part = reinterpret_cast<float*>(cursor);
+      cursor += align256(p.n_chunk * d * (int64_t)sizeof(float));
+    }
+    chunks += p.n_chunk; multis += p.n_multi;
+    b.chunk_end[k] = chunks; b.multi_end[k] = multis;
+  }
+  b.count = n_problems;
+  hipStream_t st = as_stream(stream);
+  const int lpr = d / 4;
+  if (chunks > 0) {
+    live_sum_chunks<<<(unsigned)((chunks * lpr + 255) / 256), 256, 0, st>>>(b);
+    SRH_LAUNCH_CHECK();
+  }
+  if (multis > 0) {
+    live_sum_finish<<<(unsigned)((multis * lpr + 255) / 256), 256, 0, st>>>(b);
+    SRH_LAUNCH_CHECK();
+  }
   return SRH_OK;
 }
 

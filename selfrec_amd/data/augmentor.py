@@ -8,7 +8,14 @@ graph -- instead of a rebuilt scipy matrix.  The next two calls a model makes
 (``data.convert_to_laplacian_mat(m)`` then ``convert_sparse_mat_to_tensor(m).cuda()``,
 SGL.py:89-96) recognise it and produce the re-normalised adjacency with one device kernel
 pair; nothing is rebuilt on the host and nothing is re-uploaded but E mask bytes.
+
+``SequenceAugmentor`` (reference data/augmentor.py:43-74) makes CL4SRec's sequence views on the host: crop, reorder and
+mask draw from the global ``random`` / ``np.random`` streams call for call as the reference does, so the same generator
+states on entry give the same arrays and the same states on exit.
 """
+import random
+from math import floor
+
 import numpy as np
 import torch
 
@@ -77,3 +84,42 @@ class GraphAugmentor:
         dead_i[drop_i] = True
         mask = (~dead_u[rows] & ~dead_i[csr.indices]).astype(np.uint8)
         return DroppedInteraction((n_users, n_items), mask)
+
+
+class SequenceAugmentor:
+    """Views of a padded (B, L) id batch; seq_len[i] >= 1 is the number of real items of row i."""
+
+    @staticmethod
+    def item_crop(seq, seq_len, crop_ratio):
+        """a window of floor(len * r) + 1 items from a start drawn with random.sample(range(len - floor(len * r)), 1),
+        moved to the front, positions 1 .. length.  -> (aug_seq, aug_pos, aug_len)"""
+        aug_seq, aug_pos, aug_len = np.zeros_like(seq), np.zeros_like(seq), []
+        for i in range(len(seq)):
+            n = int(seq_len[i])
+            cut = floor(n * crop_ratio)
+            start = random.sample(range(n - cut), 1)[0]
+            length = cut + 1
+            aug_seq[i, :length] = seq[i, start:start + length]
+            aug_pos[i, :length] = np.arange(1, length + 1)
+            aug_len.append(length)
+        return aug_seq, aug_pos, aug_len
+
+    @staticmethod
+    def item_reorder(seq, seq_len, reorder_ratio):
+        """the same start draw, then np.random.shuffle of the slice [start, start + floor(len * r) + 1)"""
+        aug_seq = seq.copy()
+        for i in range(len(seq)):
+            n = int(seq_len[i])
+            cut = floor(n * reorder_ratio)
+            start = random.sample(range(n - cut), 1)[0]
+            np.random.shuffle(aug_seq[i, start:start + cut + 1])
+        return aug_seq
+
+    @staticmethod
+    def item_mask(seq, seq_len, mask_ratio, mask_idx):
+        """random.sample(range(len), floor(len * r)) positions become mask_idx"""
+        aug_seq = seq.copy()
+        for i in range(len(seq)):
+            n = int(seq_len[i])
+            aug_seq[i, random.sample(range(n), floor(n * mask_ratio))] = mask_idx
+        return aug_seq

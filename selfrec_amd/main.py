@@ -3,6 +3,7 @@
     python -m selfrec_amd.main XSimGCL [--conf conf/XSimGCL.yaml] [--synthetic yelp2018]
     python -m selfrec_amd.main SASRec --synthetic beauty-seq
     python -m selfrec_amd.main BERT4Rec --synthetic beauty-seq
+    python -m selfrec_amd.main CL4SRec --synthetic beauty-seq
 
 ``--synthetic SHAPE`` writes a generated dataset of that shape (selfrec_amd/synth.py) to the
 paths the config names, if they do not exist yet -- the reference's dataset files are not
@@ -16,7 +17,7 @@ from . import synth
 from .SELFRec import SELFRec
 from .util.conf import ModelConf
 
-MODELS = ['MF', 'LightGCN', 'XSimGCL', 'SimGCL', 'SGL', 'DirectAU', 'MixGCF', 'BUIR', 'SelfCF', 'NCL', 'UserKNN', 'ItemKNN', 'SSL4Rec', 'SASRec', 'BERT4Rec']
+MODELS = ['MF', 'LightGCN', 'XSimGCL', 'SimGCL', 'SGL', 'DirectAU', 'MixGCF', 'BUIR', 'SelfCF', 'NCL', 'UserKNN', 'ItemKNN', 'SSL4Rec', 'SASRec', 'BERT4Rec', 'CL4SRec']
 
 
 def main(argv=None):

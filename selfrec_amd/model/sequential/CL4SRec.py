@@ -1,0 +1,265 @@
+"""CL4SRec (Xie et al., ICDE'22; reference model/sequential/CL4SRec.py): SASRec's encoder and BCE loss plus an InfoNCE term
+between the last hidden rows of two augmented views of every sequence (crop, reorder or mask: data/augmentor.py's
+SequenceAugmentor).  Config block ``CL4SRec: {n_blocks, drop_rate, n_heads, aug_type, aug_rate, cl_rate}``, ``max.len``.
+
+What runs where:
+  * ``engine.views: one`` (default; ``SRH_CL4SREC_VIEWS``) stacks [batch; view 1; view 2] into ONE (3B, L) batch and runs
+    the encoder once: padding sits on the right and the mask is causal, so no sequence sees another and the result is the
+    three calls' in exact arithmetic.  ``three`` is the reference's three calls, the A/B partner.
+  * ``engine.embed: hip`` (default; ``SRH_CL4SREC_EMBED``) takes the embedding front -- both gathers, scale, sum, dropout,
+    padding mask -- as one launch (ops.SeqEmbedFn) whose two table gradients, like the BCE's (ops.SeqBceLiveFn), are summed
+    over the LIVE rows only in chunks of fixed length (srh_rows_live_sum_f32).  ``torch`` is SASRec_Model.forward's front
+    (ops.GatherRowsFn twice, mul, add, dropout, mask) and ops.SeqBceFn: the parent's route.
+  * ``engine.attention`` as in SASRec; the InfoNCE of the two (B, d) row sets is ops.InfoNceFn (util.loss_torch.InfoNCE for
+    a width that entry does not take).  A model on the CPU takes torch's expressions throughout.
+
+The item table has item_num + 2 rows (item_num + 1: the mask token) and is created AFTER the rest of the network, as the
+reference replaces it, so ``torch.manual_seed`` reproduces its initial weights and the state_dict order.
+
+Host work of a step: ``StagedViews`` turns the stacked ids and positions, y, neg, the last-row indices of both views and
+every plan the routes need into ONE int32 upload."""
+import os
+
+import numpy as np
+import torch
+import torch.nn as nn
+
+from ... import ops
+from ...base.seq_recommender import SequentialRecommender
+from ...data.augmentor import SequenceAugmentor
+from ...util.loss_torch import InfoNCE, l2_reg_loss
+from ...util.sampler import next_batch_sequence
+from .SASRec import SASRec, SASRec_Model, attention_route
+
+
+def _route(env, key, conf, choices):
+    route = os.environ.get(env)
+    if route is None and conf is not None and conf.contain(key):
+        route = conf[key]
+    route = choices[0] if route is None else str(route).strip().lower()
+    if route not in choices:
+        raise ValueError(f"{key} / {env}: {route!r} is neither {choices[0]!r} nor {choices[1]!r}")
+    return route
+
+
+def views_route(conf=None):
+    """'one' or 'three': SRH_CL4SREC_VIEWS, else the conf's engine.views, else one stacked encoder pass"""
+    return _route('SRH_CL4SREC_VIEWS', 'engine.views', conf, ('one', 'three'))
+
+
+def embed_route(conf=None):
+    """'hip' or 'torch': SRH_CL4SREC_EMBED, else the conf's engine.embed, else the kernels"""
+    return _route('SRH_CL4SREC_EMBED', 'engine.embed', conf, ('hip', 'torch'))
+
+
+class _Group:
+    """one encoder pass of a StagedViews: ids, positions, the padding mask and the two plans of its gathers"""
+    __slots__ = ('shape', 'seq', 'pos', 'plans', 'live')
+
+
+class StagedViews:
+    """One training step on the device.  ``views`` = [(seq, pos, last)] * 3: the batch and its two augmented views, ``last``
+    the 1-based position of the row InfoNCE reads (None for the batch).  views='one' makes one group of the stacked
+    (3B, L) arrays, 'three' one group per view; embed='hip' builds live plans (ops.live_plan_host), 'torch' the scatter
+    plans of ops.GatherRowsFn / ops.SeqBceFn.  Everything travels in one int32 upload."""
+
+    def __init__(self, views, y, neg, device, route_views='one', route_embed='hip'):
+        seqs = [np.asarray(v[0]) for v in views]
+        poss = [np.asarray(v[1]) for v in views]
+        B, L = seqs[0].shape
+        self.B, self.L, self.route_views, self.route_embed = B, L, route_views, route_embed
+        seq_all = np.concatenate([s.reshape(-1) for s in seqs])
+        pos_all = np.concatenate([p.reshape(-1) for p in poss])
+        y, neg = np.asarray(y).reshape(-1), np.asarray(neg).reshape(-1)
+        valid = poss[0].reshape(-1) != 0
+        per = B * L
+        bounds = [(0, len(views) * per)] if route_views == 'one' else [(v * per, (v + 1) * per) for v in range(len(views))]
+        # the row of the hidden states each view's InfoNCE reads, as an index into its group's (rows, d) hidden matrix
+        lasts = []
+        for v in (1, 2):
+            base = v * B if route_views == 'one' else 0
+            lasts.append((base + np.arange(B)) * L + np.asarray(views[v][2], dtype=np.int64) - 1)
+        hip = route_embed == 'hip'
+        plans = []
+        for lo, hi in bounds:
+            s, p = seq_all[lo:hi], pos_all[lo:hi]
+            plans += [ops.live_plan_host(s, s != 0), ops.live_plan_host(p, s != 0)] if hip else \
+                     [ops.scatter_plan_host(s), ops.scatter_plan_host(p)]
+        yn = np.concatenate([y, neg])
+        plans.append(ops.live_plan_host(yn, np.concatenate([valid, valid])) if hip else ops.scatter_plan_host(yn))
+        head = [seq_all, pos_all, y, neg, lasts[0], lasts[1]]
+        parts = [np.ascontiguousarray(a, dtype=np.int32) for a in head] + [a for plan in plans for a in plan]
+        flat = torch.from_numpy(np.concatenate(parts)).to(device)
+        cut, at = [], 0
+        for a in parts:
+            cut.append(flat[at:at + a.size])
+            at += a.size
+        self.y, self.neg, self.last = cut[2], cut[3], (cut[4], cut[5])
+        width = 5 if hip else 3
+        dev_plans = [tuple(cut[len(head) + width * k:len(head) + width * (k + 1)]) for k in range(len(plans))]
+        self.groups = []
+        for k, (lo, hi) in enumerate(bounds):
+            g = _Group()
+            g.shape = ((hi - lo) // L, L)
+            g.seq, g.pos = cut[0][lo:hi], cut[1][lo:hi]
+            g.plans = (dev_plans[2 * k], dev_plans[2 * k + 1])
+            g.live = (g.seq != 0).reshape(*g.shape, 1)
+            self.groups.append(g)
+        self.bce_plan = dev_plans[-1]
+        self.valid = (cut[1][:per] != 0).to(torch.uint8)
+        self.n_valid = int(np.count_nonzero(valid))
+        self.live_share = float(np.count_nonzero(seq_all)) / seq_all.size
+
+
+class CL4SRec(SequentialRecommender):
+    def __init__(self, conf, training_set, test_set):
+        super(CL4SRec, self).__init__(conf, training_set, test_set)
+        section = self.config['CL4SRec']
+        self.aug_type = int(section['aug_type'])
+        self.aug_rate = float(section['aug_rate'])
+        self.cl_rate = float(section['cl_rate'])
+        self.views, self.embed = views_route(conf), embed_route(conf)
+        self.model = CL4SRec_Model(self.data, self.emb_size, self.max_len, int(section['n_blocks']),
+                                   int(section['n_heads']), float(section['drop_rate']), attention=attention_route(conf))
+        self.rec_loss = torch.nn.BCEWithLogitsLoss()
+        self.epoch_losses = []
+
+    def augment(self, seq, pos, seq_len):
+        """the step's two views, drawn in the reference's order: [(seq, pos, last)] * 2"""
+        out = []
+        for _ in range(2):
+            if self.aug_type == 0:
+                out.append(SequenceAugmentor.item_crop(seq, seq_len, self.aug_rate))
+            elif self.aug_type == 1:
+                out.append((SequenceAugmentor.item_reorder(seq, seq_len, self.aug_rate), pos, seq_len))
+            else:
+                out.append((SequenceAugmentor.item_mask(seq, seq_len, self.aug_rate, self.data.item_num + 1), pos, seq_len))
+        return out
+
+    def train(self):
+        net = self.model.cuda()
+        adam = torch.optim.Adam(net.parameters(), lr=self.lRate)
+        for epoch in range(self.maxEpoch):
+            net.train()
+            seen = []
+            batches = next_batch_sequence(self.data, self.batch_size, max_len=self.max_len)
+            for n, (seq, pos, y, neg_idx, seq_len) in enumerate(batches):
+                batch_loss, rec_loss, _ = self.step_losses(seq, pos, y, neg_idx, self.augment(seq, pos, seq_len))
+                adam.zero_grad()
+                batch_loss.backward()
+                adam.step()
+                seen.append(batch_loss.detach())
+                if n % 50 == 0:
+                    print('training:', epoch + 1, 'batch', n, 'batch_loss:', batch_loss.item(), 'rec_loss:', rec_loss.item())
+            self.epoch_losses.append([float(v) for v in torch.stack(seen).cpu()])
+            net.eval()
+            self.fast_evaluation(epoch)
+
+    def step_losses(self, seq, pos, y, neg, aug_views):
+        """(batch loss, rec loss, cl_rate * InfoNCE) of one batch and its two views ([(seq, pos, last)] * 2)"""
+        net = self.model
+        dev = net.item_emb.device
+        d = self.emb_size
+        if dev.type != 'cuda':
+            hidden = net.forward(seq, pos)
+            rows = []
+            for v_seq, v_pos, v_last in aug_views:
+                emb = net.forward(v_seq, v_pos)
+                last = torch.as_tensor(np.asarray(v_last, dtype=np.int64) - 1)
+                rows.append(emb[torch.arange(emb.shape[0]), last])
+            rec_loss = self.calculate_loss(hidden, y, neg, pos)
+        else:
+            staged = StagedViews([(seq, pos, None)] + list(aug_views), y, neg, dev, self.views, self.embed)
+            B = staged.B
+            if self.views == 'one':
+                out = net.forward(None, None, staged=staged, group=0).reshape(-1, d)
+                hidden, rows = out[:B * staged.L], [out[staged.last[v].long()] for v in range(2)]
+            else:
+                hidden = net.forward(None, None, staged=staged, group=0).reshape(-1, d)
+                rows = [net.forward(None, None, staged=staged, group=v + 1).reshape(-1, d)[staged.last[v].long()]
+                        for v in range(2)]
+            rec_loss = self.calculate_loss(hidden, y, neg, pos, staged=staged)
+        if rows[0].is_cuda and d in ops.NCE_WIDTHS:
+            cl = ops.InfoNceFn.apply(rows[0], rows[1], 1.0)
+        else:
+            cl = InfoNCE(rows[0], rows[1], 1, True)
+        cl_loss = self.cl_rate * cl
+        return rec_loss + l2_reg_loss(self.reg, net.item_emb) + cl_loss, rec_loss, cl_loss
+
+    def calculate_loss(self, seq_emb, y, neg, pos, staged=None):
+        """both BCE-with-logits means over the positions with pos != 0 (CL4SRec.py:70-79)"""
+        table = self.model.item_emb
+        hidden = seq_emb.reshape(-1, seq_emb.shape[-1])
+        if not hidden.is_cuda:
+            idx = torch.from_numpy(np.flatnonzero(np.asarray(pos).reshape(-1) != 0))
+            h = hidden[idx]
+            yp = torch.from_numpy(np.asarray(y).reshape(-1).astype(np.int64))[idx]
+            yn = torch.from_numpy(np.asarray(neg).reshape(-1).astype(np.int64))[idx]
+            pos_logits, neg_logits = (h * table[yp]).sum(-1), (h * table[yn]).sum(-1)
+            return (self.rec_loss(pos_logits, torch.ones_like(pos_logits))
+                    + self.rec_loss(neg_logits, torch.zeros_like(neg_logits)))
+        if staged is not None:
+            fn = ops.SeqBceLiveFn if staged.route_embed == 'hip' else ops.SeqBceFn
+            return fn.apply(hidden, table, staged.y, staged.neg, staged.valid, staged.n_valid, staged.bce_plan)
+        dev = hidden.device
+        y, neg, valid = np.asarray(y).reshape(-1), np.asarray(neg).reshape(-1), np.asarray(pos).reshape(-1) != 0
+        yn = np.concatenate([y, neg])
+        ids = torch.from_numpy(np.stack([y, neg, valid]).astype(np.int32)).to(dev)
+        if self.embed == 'hip':
+            fn, plan = ops.SeqBceLiveFn, ops.live_plan(yn, dev, np.concatenate([valid, valid]))
+        else:
+            fn, plan = ops.SeqBceFn, ops.scatter_plan(yn, dev)
+        return fn.apply(hidden, table, ids[0], ids[1], ids[2].to(torch.uint8), int(np.count_nonzero(valid)), plan)
+
+    last_hidden = SASRec.last_hidden
+    item_table = SASRec.item_table
+    predict = SASRec.predict
+
+
+class CL4SRec_Model(SASRec_Model):
+    """SASRec_Model with the item_num + 2-row item table and a front that reads a StagedViews group"""
+
+    def _init_model(self):
+        super()._init_model()
+        # the reference replaces the table once the network stands (CL4SRec.py:23-25): the same draws in the same order
+        self.item_emb = nn.Parameter(nn.init.xavier_uniform_(torch.empty(self.data.item_num + 2, self.emb_size)))
+
+    def uses_embed_kernel(self, staged):
+        return staged.route_embed == 'hip' and ops.seq_embed_supported(self.emb_size)
+
+    def forward(self, seq, pos, attn_keep=None, staged=None, group=0, emb_keep=None):
+        """(rows, L, d) hidden states.  Without ``staged`` (evaluation, a CPU model): SASRec_Model.forward on the id arrays.
+        With it: the encoder over staged.groups[group]; emb_keep: an optional (rows, L, d) keep mask of the embedding
+        dropout, replayed instead of drawn."""
+        if staged is None:
+            return super().forward(seq, pos, attn_keep)
+        g = staged.groups[group]
+        B, L = g.shape
+        d = self.emb_size
+        p = float(self.drop_rate) if self.training else 0.0
+        if self.uses_embed_kernel(staged):
+            seq_emb = ops.SeqEmbedFn.apply(self.item_emb, self.pos_emb, g.seq, g.pos, g.plans[0], g.plans[1], emb_keep, p,
+                                           self.rng_seed, self.rng_counter).reshape(B, L, d)
+            if emb_keep is None and p > 0.0:
+                self.rng_counter += B * L
+        else:
+            if staged.route_embed == 'hip':
+                raise ops.SelfrecHipError(f"engine.embed: hip serves widths {ops.SEQ_EMBED_WIDTHS}, not {d}")
+            items = ops.GatherRowsFn.apply(self.item_emb, g.seq, g.plans[0])
+            places = ops.GatherRowsFn.apply(self.pos_emb, g.pos, g.plans[1])
+            seq_emb = (items * d ** 0.5 + places).reshape(B, L, d)
+            if emb_keep is not None:
+                seq_emb = seq_emb * (emb_keep.reshape(B, L, d).to(seq_emb.dtype) / (1.0 - p))
+            else:
+                seq_emb = self.emb_dropout(seq_emb)
+            seq_emb = seq_emb * g.live
+        live = g.live
+        for i in range(len(self.attention_layers)):
+            normalized_emb = self.attention_layer_norms[i](seq_emb)
+            keep = None if attn_keep is None else attn_keep[i]
+            mha_outputs = self._attention(self.attention_layers[i], normalized_emb, seq_emb, keep)
+            seq_emb = normalized_emb + mha_outputs
+            seq_emb = self.forward_layer_norms[i](seq_emb)
+            seq_emb = self.forward_layers[i](seq_emb)
+            seq_emb = seq_emb * live
+        return self.last_layer_norm(seq_emb)

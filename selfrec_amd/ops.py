@@ -28,6 +28,7 @@ __all__ = ["Sampler", "DeviceCSR", "column_class_order", "spmm", "spmm_any", "pa
            "tower_fwd", "tower_bwd", "scatter_plan", "scatter_plan_host", "rows_segment_sum", "batch_softmax_fwd_bwd", "TowerFn",
            "BatchSoftmaxFn", "seq_attn_supported", "seq_attn_fwd", "seq_attn_bwd", "SeqAttnFn", "seq_bce_fwd_bwd", "SeqBceFn",
            "GatherRowsFn", "seq_attn_full_fwd", "seq_attn_full_bwd", "SeqAttnFullFn", "table_ce_fwd_bwd", "TableCeFn",
+           "seq_embed_fwd", "live_plan_host", "live_plan", "rows_live_sum", "SeqEmbedFn", "SeqBceLiveFn", "InfoNceFn",
            "SelfrecHipError"]
 
 
@@ -1655,3 +1656,177 @@ class TableCeFn(torch.autograd.Function):
     def backward(ctx, gout):
         gh, gt = ctx.saved_tensors
         return gh * gout, gt * gout, None, None
+
+
+# ---- CL4SRec (csrc/seqrec.hip: the embedding front and the live-row table gradient) ---------------------------------------
+SEQ_EMBED_WIDTHS = (32, 64, 128)              # srh_seq_embed_fwd_f32 / srh_rows_live_sum_f32
+LIVE_SUM_CHUNK = 32                           # SRH_LIVE_SUM_CHUNK
+LIVE_SUM_MAX_PROBLEMS = 3                     # SRH_LIVE_SUM_MAX_PROBLEMS
+_U64 = 0xFFFFFFFFFFFFFFFF
+
+
+def seq_embed_supported(d: int) -> bool:
+    return int(d) in SEQ_EMBED_WIDTHS
+
+
+def seq_embed_fwd(item, pos_table, seq, posid, *, scale=None, keep=None, drop_p=0.0, rng_seed=0, rng_counter=0):
+    """(R x d) rows (item[seq[r]] * scale + pos_table[posid[r]]) * m(r) for the rows with seq[r] != 0, exact zeros for the
+    others (include/selfrec_hip.h (a-18)).  seq / posid: int32 device tensors of R entries; scale defaults to sqrt(d);
+    ``keep`` ((R, d), 1 = keep) replays a dropout mask, without it and with drop_p > 0 the mask is drawn in-kernel at the
+    counters [rng_counter, rng_counter + R)."""
+    if item.dim() != 2 or pos_table.dim() != 2 or item.shape[1] != pos_table.shape[1]:
+        raise SelfrecHipError("seq_embed: item (n x d) and position (m x d) tables expected")
+    R, d = int(seq.numel()), int(item.shape[1])
+    if int(posid.numel()) != R or R < 1:
+        raise SelfrecHipError(f"seq_embed: {R} item ids and {int(posid.numel())} position ids")
+    if keep is not None:
+        if int(keep.numel()) != R * d:
+            raise SelfrecHipError(f"seq_embed: keep mask of {int(keep.numel())} entries, expected {R} x {d}")
+        keep = keep.to(torch.uint8).contiguous()
+    out = torch.empty((R, d), dtype=torch.float32, device=item.device)
+    check(_lib.load().srh_seq_embed_fwd_f32(_p(item, torch.float32, "item"), int(item.shape[0]),
+                                            _p(pos_table, torch.float32, "pos_table"), int(pos_table.shape[0]),
+                                            _p(seq, torch.int32, "seq"), _p(posid, torch.int32, "posid"), R, d,
+                                            float(d ** 0.5 if scale is None else scale), _p(keep, torch.uint8, "keep"),
+                                            int(rng_seed) & _U64, int(rng_counter) & _U64, float(drop_p), _p(out),
+                                            _stream()), "srh_seq_embed_fwd_f32")
+    return out
+
+
+def live_plan_host(ids, live=None, chunk=LIVE_SUM_CHUNK):
+    """The plan of srh_rows_live_sum_f32 for gathered-row ids (host array): the rows with ``live`` (default ids != 0)
+    sorted stably by id, every id's segment cut into chunks of at most ``chunk`` rows.
+    -> (rows, chunk_start, chunk_dst, multi_range, multi_row) int32 host arrays (include/selfrec_hip.h (a-18))."""
+    ids = np.ascontiguousarray(np.asarray(ids).reshape(-1), dtype=np.int64)
+    live = ids != 0 if live is None else np.asarray(live).reshape(-1).astype(bool)
+    rows = np.flatnonzero(live)
+    rows = rows[np.argsort(ids[rows], kind="stable")]
+    s = ids[rows]
+    first = np.flatnonzero(np.r_[True, s[1:] != s[:-1]]) if s.size else np.zeros(0, dtype=np.int64)
+    length = np.diff(np.r_[first, s.size])
+    n_chunks = (length + chunk - 1) // chunk                                     # chunks per segment
+    chunk0 = np.r_[0, np.cumsum(n_chunks)].astype(np.int64)                      # first chunk of each segment
+    seg_of_chunk = np.repeat(np.arange(first.size), n_chunks)
+    within = np.arange(int(chunk0[-1])) - chunk0[seg_of_chunk]
+    chunk_start = np.r_[first[seg_of_chunk] + within * chunk, s.size] if s.size else np.zeros(1, dtype=np.int64)
+    chunk_dst = np.where(n_chunks[seg_of_chunk] == 1, s[first][seg_of_chunk], -1)
+    multi = np.flatnonzero(n_chunks > 1)
+    multi_range = np.stack([chunk0[multi], chunk0[multi + 1]], axis=1).reshape(-1)
+    multi_row = s[first][multi]
+    return tuple(np.ascontiguousarray(a, dtype=np.int32) for a in (rows, chunk_start, chunk_dst, multi_range, multi_row))
+
+
+def live_plan(ids, device, live=None, chunk=LIVE_SUM_CHUNK):
+    """live_plan_host's five arrays as int32 device tensors"""
+    return tuple(torch.from_numpy(a).to(device) for a in live_plan_host(ids, live, chunk))
+
+
+def rows_live_sum(problems):
+    """srh_rows_live_sum_f32 over 1..3 problems, each a dict(x=(n x d), plan=live_plan(...), out=(table x d)[, scale=1.0,
+    keep=None, drop_p=0.0, rng_seed=0, rng_counter=0]): out[row] = scale * the sum of the rows of x the plan lists for it,
+    each times its dropout multiplier, in plan order.  Rows of out the plan does not name are left as they are."""
+    lib = _lib.load()
+    if not 1 <= len(problems) <= LIVE_SUM_MAX_PROBLEMS:
+        raise SelfrecHipError(f"rows_live_sum: 1..{LIVE_SUM_MAX_PROBLEMS} problems per call")
+    arr = (_lib.LiveSumProblem * len(problems))()
+    d = int(problems[0]["x"].shape[1])
+    hold = []
+    for k, pr in enumerate(problems):
+        x, out = pr["x"], pr["out"]
+        rows, chunk_start, chunk_dst, multi_range, multi_row = pr["plan"]
+        if x.dim() != 2 or out.dim() != 2 or int(x.shape[1]) != d or int(out.shape[1]) != d:
+            raise SelfrecHipError("rows_live_sum: x (n x d) and out (table x d) of one width expected")
+        n_chunk, n_multi = int(chunk_dst.numel()), int(multi_row.numel())
+        if int(chunk_start.numel()) != n_chunk + 1 or int(multi_range.numel()) != 2 * n_multi:
+            raise SelfrecHipError("rows_live_sum: the plan's arrays do not match")
+        keep = pr.get("keep")
+        if keep is not None:
+            if int(keep.numel()) != int(x.shape[0]) * d:
+                raise SelfrecHipError("rows_live_sum: the keep mask does not match x")
+            keep = keep.to(torch.uint8).contiguous()
+        x = x.contiguous()
+        hold += [x, keep]
+        a = arr[k]
+        a.d_x, a.n_rows = _p(x, torch.float32, "x"), int(x.shape[0])
+        a.d_rows, a.d_chunk_start = _p(rows, torch.int32, "rows"), _p(chunk_start, torch.int32, "chunk_start")
+        a.d_chunk_dst = _p(chunk_dst, torch.int32, "chunk_dst")
+        a.d_multi_range, a.d_multi_row = _p(multi_range, torch.int32, "multi_range"), _p(multi_row, torch.int32, "multi_row")
+        a.n_live, a.n_chunk, a.n_multi = int(rows.numel()), n_chunk, n_multi
+        a.d_out, a.n_table = _p(out, torch.float32, "out"), int(out.shape[0])
+        a.scale, a.drop_p = float(pr.get("scale", 1.0)), float(pr.get("drop_p", 0.0))
+        a.d_keep = _p(keep, torch.uint8, "keep")
+        a.rng_seed, a.rng_counter = int(pr.get("rng_seed", 0)) & _U64, int(pr.get("rng_counter", 0)) & _U64
+    need = int(lib.srh_rows_live_sum_ws_bytes(arr, len(problems), d))
+    ws = torch.empty(need, dtype=torch.uint8, device=problems[0]["x"].device) if need else None
+    check(lib.srh_rows_live_sum_f32(arr, len(problems), d, _p(ws), _stream()), "srh_rows_live_sum_f32")
+    return [pr["out"] for pr in problems]
+
+
+class SeqEmbedFn(torch.autograd.Function):
+    """The embedding front of the sequence encoder as one launch (seq_embed_fwd); both table gradients come from ONE
+    rows_live_sum call over the live rows only: the item plan with scale sqrt(d), the position plan with scale 1, the
+    dropout multiplier redrawn from the forward's arguments.  item_plan / pos_plan: live_plan of the item / position ids
+    with live = (seq != 0)."""
+
+    @staticmethod
+    def forward(ctx, item, pos_table, seq, posid, item_plan, pos_plan, keep, drop_p, rng_seed, rng_counter):
+        ctx.args = (seq, item_plan, pos_plan, keep, drop_p, rng_seed, rng_counter, tuple(item.shape), tuple(pos_table.shape))
+        return seq_embed_fwd(item, pos_table, seq, posid, keep=keep, drop_p=drop_p, rng_seed=rng_seed,
+                             rng_counter=rng_counter)
+
+    @staticmethod
+    def backward(ctx, g):
+        seq, item_plan, pos_plan, keep, drop_p, rng_seed, rng_counter, item_shape, pos_shape = ctx.args
+        d = item_shape[1]
+        g = g.reshape(-1, d).to(torch.float32).contiguous()
+        gi = torch.zeros(item_shape, dtype=torch.float32, device=g.device)
+        gp = torch.zeros(pos_shape, dtype=torch.float32, device=g.device)
+        drop = dict(keep=keep, drop_p=drop_p, rng_seed=rng_seed, rng_counter=rng_counter)
+        rows_live_sum([dict(x=g, plan=item_plan, out=gi, scale=d ** 0.5, **drop), dict(x=g, plan=pos_plan, out=gp, **drop)])
+        return gi, gp, None, None, None, None, None, None, None, None
+
+
+class SeqBceLiveFn(torch.autograd.Function):
+    """SeqBceFn with the item table's gradient summed over the valid rows of [pos; neg] only (``plan`` = live_plan of
+    [pos; neg] with live = [valid; valid]): the rows the kernel zeroed are never walked."""
+
+    @staticmethod
+    def forward(ctx, hidden, table, pos, neg, valid, n_valid, plan):
+        loss2, gh, grows = seq_bce_fwd_bwd(hidden.contiguous(), table, pos, neg, valid, n_valid)
+        ctx.save_for_backward(gh, grows)
+        ctx.plan, ctx.table_shape = plan, tuple(table.shape)
+        return (loss2[0].to(torch.float32) + loss2[1].to(torch.float32))
+
+    @staticmethod
+    def backward(ctx, gout):
+        gh, grows = ctx.saved_tensors
+        gt = torch.zeros(ctx.table_shape, dtype=torch.float32, device=gh.device)
+        rows_live_sum([dict(x=grows, plan=ctx.plan, out=gt)])
+        return gh * gout, gt * gout, None, None, None, None, None
+
+
+class InfoNceFn(torch.autograd.Function):
+    """util/loss_torch.py InfoNCE(v1, v2, tau, b_cos=True) of two (n x d) row sets as one differentiable op over
+    srh_infonce_fwd_bwd_multi (idx = NULL: row i of the gradients belongs to row i).  The gradients start at zero and g2 is
+    a table of its own, so it is declared exclusive: plain stores instead of float atomics.  d in NCE_WIDTHS."""
+
+    @staticmethod
+    def forward(ctx, v1, v2, tau):
+        n, d = int(v1.shape[0]), int(v1.shape[1])
+        if v1.shape != v2.shape or d not in NCE_WIDTHS:
+            raise SelfrecHipError(f"InfoNceFn: two (n x d) views with d in {NCE_WIDTHS} expected")
+        v1, v2 = v1.to(torch.float32).contiguous(), v2.to(torch.float32).contiguous()
+        dev = v1.device
+        buf = torch.zeros(2 * n * d + 2, dtype=torch.float32, device=dev)       # [g1 | g2 | loss (one double)]
+        g = buf[:2 * n * d].view(2, n, d)
+        loss = buf[2 * n * d:].view(torch.float64)
+        infonce_multi([(v1, v2, None, n, None, g[0], g[1], True)], d=d, tau=float(tau), loss_scale=1.0, loss=loss,
+                      ws=infonce_ws(n, d, dev))
+        ctx.save_for_backward(g)
+        return loss.to(torch.float32).reshape(())
+
+    @staticmethod
+    def backward(ctx, gout):
+        (g,) = ctx.saved_tensors
+        g = g * gout
+        return g[0], g[1], None
