@@ -873,6 +873,11 @@ srh_status_t srh_batch_softmax_fwd_bwd(const float* d_u, const float* d_v, int64
  *   summed in a fixed order).  d_gh (R x d): d(loss2[0] + loss2[1]) / dh; d_grows (2R x d): row r the gradient the row
  *   contributes to table[pos[r]], row R + r to table[neg[r]] (zero rows where invalid) -- srh_rows_segment_sum_f32 over
  *   [pos; neg] makes the table gradient.  d_ws >= srh_seq_bce_ws_bytes(R).
+ *   Any 1 <= d <= 1024, any R >= 1.  A row with d_valid[r] != 0 whose pos[r] or neg[r] lies outside [0, n_table) is
+ *   treated as invalid: the ids are tested before any address is formed, no table row is read for it, it adds nothing to
+ *   either loss and takes exact zeros in d_gh and in both of its d_grows rows.  n_valid stays the caller's divisor: to
+ *   keep the means over the rows that count, the caller leaves such rows out of it.  n_valid outside [1, R] is refused
+ *   (SRH_ERR_INVALID_ARG) before any launch.
  * ---------------------------------------------------------------------------------- */
 srh_status_t srh_seq_attn_fwd_f32(const float* d_q, const float* d_k, const float* d_v, int64_t B, int32_t L, int32_t H,
                                   int32_t dh, const uint8_t* d_keep, uint64_t rng_seed, uint64_t rng_counter, float drop_p,

@@ -15,12 +15,14 @@ import numpy as np
 import pytest
 import torch
 
-from tests import bert4rec_ref
+from tests import bert4rec_ref, seq_attn_ref
 from tests.test_shapes_cpu import GOLDEN
 
 pytestmark = pytest.mark.gpu
 
-ATTN_SHAPES = [(1, 1, 1, 64), (3, 7, 1, 64), (2, 16, 1, 64), (2, 17, 2, 32), (2, 33, 2, 64), (5, 50, 1, 64), (4, 64, 2, 32)]
+ATTN_SHAPES = [(1, 1, 1, 64), (3, 7, 1, 64), (2, 16, 1, 64), (2, 17, 2, 32), (2, 33, 2, 64), (5, 50, 1, 64), (4, 64, 2, 32),
+               # the remaining tile edges, and the head layouts where the head offset and the row stride differ
+               (2, 31, 3, 32), (2, 32, 4, 32), (2, 48, 1, 32), (2, 49, 2, 64), (2, 63, 1, 64)]
 DROP_P = 0.2
 
 
@@ -44,7 +46,7 @@ def attn_case(shape, masked):
     out.backward(go.double())
     p = torch.softmax(q64.detach()[..., :dh] @ k64.detach()[..., :dh].transpose(1, 2) / dh ** 0.5, -1)
     return dict(q=q, k=k, v=v, go=go, keep=keep, out=out.detach(), gq=q64.grad, gk=k64.grad, gv=v64.grad,
-                peak=float(p.max()))
+                lse=seq_attn_ref.lse(q, k, H, False), peak=float(p.max()))
 
 
 @pytest.mark.parametrize("masked", [False, True], ids=["plain", "keep"])
@@ -67,8 +69,9 @@ def test_full_attention_forward_and_backward_match_float64(shape, masked):
         errs = dict(out=rel_err(out, c["out"]), gq=0.0, gk=0.0, gv=rel_err(gv, c["gv"]))
     else:
         errs = dict(out=rel_err(out, c["out"]), gq=rel_err(gq, c["gq"]), gk=rel_err(gk, c["gk"]), gv=rel_err(gv, c["gv"]))
+    errs["lse"] = rel_err(lse, c["lse"])
     print(shape, masked, errs)
-    assert errs["out"] <= 1e-5, errs
+    assert errs["out"] <= 1e-5 and errs["lse"] <= 1e-5, errs
     assert max(errs["gq"], errs["gk"], errs["gv"]) <= 1e-4, errs
     # the autograd wrapper is the same two calls
     qa, ka, va = (t.clone().requires_grad_(True) for t in (q, k, v))

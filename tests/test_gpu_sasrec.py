@@ -12,12 +12,14 @@ import numpy as np
 import pytest
 import torch
 
-from tests import sasrec_ref
+from tests import sasrec_ref, seq_attn_ref
 from tests.test_shapes_cpu import GOLDEN
 
 pytestmark = pytest.mark.gpu
 
-ATTN_SHAPES = [(1, 1, 1, 64), (3, 7, 1, 64), (5, 50, 1, 64), (4, 64, 2, 32), (2, 33, 2, 64), (256, 50, 1, 64)]
+ATTN_SHAPES = [(1, 1, 1, 64), (3, 7, 1, 64), (5, 50, 1, 64), (4, 64, 2, 32), (2, 33, 2, 64), (256, 50, 1, 64),
+               # either side of the 16-row tile edges, and the head layouts where the head offset and the row stride differ
+               (2, 16, 1, 64), (2, 17, 2, 32), (2, 32, 4, 32), (2, 48, 1, 32), (2, 49, 3, 32)]
 DROP_P = 0.2
 
 
@@ -41,7 +43,7 @@ def attn_case(shape, masked):
     p = torch.softmax((q64.detach()[..., :dh] @ k64.detach()[..., :dh].transpose(1, 2) / dh ** 0.5)
                       .masked_fill(~torch.ones(L, L, dtype=torch.bool).tril(), float('-inf')), -1)
     return dict(q=q, k=k, v=v, go=go, keep=keep, out=out.detach(), gq=q64.grad, gk=k64.grad, gv=v64.grad,
-                peak=float(p[:, L // 2:].max(-1).values.max()))       # (row 0 is one-hot by construction: later rows only)
+                lse=seq_attn_ref.lse(q, k, H, True), peak=float(p[:, L // 2:].max(-1).values.max()))       # (row 0 is one-hot by construction: later rows only)
 
 
 @pytest.mark.parametrize("masked", [False, True], ids=["plain", "keep"])
@@ -64,8 +66,9 @@ def test_attention_forward_and_backward_match_float64(shape, masked):
         errs = dict(out=rel_err(out, c["out"]), gq=0.0, gk=0.0, gv=rel_err(gv, c["gv"]))
     else:
         errs = dict(out=rel_err(out, c["out"]), gq=rel_err(gq, c["gq"]), gk=rel_err(gk, c["gk"]), gv=rel_err(gv, c["gv"]))
+    errs["lse"] = rel_err(lse, c["lse"])
     print(shape, masked, errs)
-    assert errs["out"] <= 1e-5, errs
+    assert errs["out"] <= 1e-5 and errs["lse"] <= 1e-5, errs
     assert max(errs["gq"], errs["gk"], errs["gv"]) <= 1e-4, errs
     # the autograd wrapper is the same two calls
     qa, ka, va = (t.clone().requires_grad_(True) for t in (q, k, v))

@@ -207,3 +207,130 @@ def test_entry_points_are_declared_and_bound():
     assert ops.seq_attn_supported(1, 1, 64) and ops.seq_attn_supported(64, 2, 64) and ops.seq_attn_supported(33, 4, 32)
     assert not ops.seq_attn_supported(65, 1, 64) and not ops.seq_attn_supported(50, 1, 48)
     assert not ops.seq_attn_supported(50, 4, 64)
+
+
+# ---- the premises of the sequence-kernel edge tests (tests/seq_attn_ref.py, tests/test_gpu_seq_edges.py) ------------------
+@pytest.mark.parametrize("causal", [True, False], ids=["causal", "full"])
+def test_restatement_lse_reproduces_the_softmax_attention_uses(causal):
+    """V = I makes attention() return its own P; exp(s - lse) is that P, and lse is the plain log of the row's sum"""
+    from tests import seq_attn_ref
+    B, L, H, dh = 2, 17, 2, 32
+    g = torch.Generator().manual_seed(11)
+    q = 3.0 * torch.randn(B, L, H * dh, generator=g, dtype=torch.float64)
+    k = torch.randn(B, L, H * dh, generator=g, dtype=torch.float64)
+    v = torch.zeros(B, L, H, dh, dtype=torch.float64)
+    v[:, torch.arange(L), :, torch.arange(L)] = 1.0
+    p = seq_attn_ref.attention(q, k, v.reshape(B, L, H * dh), H, causal).reshape(B, L, H, dh)[..., :L].permute(0, 2, 1, 3)
+    lse = seq_attn_ref.lse(q, k, H, causal)
+    assert lse.shape == (B, H, L) and lse.dtype == torch.float64
+    s = torch.stack([q[..., h * dh:(h + 1) * dh] @ k[..., h * dh:(h + 1) * dh].transpose(1, 2) for h in range(H)], 1) / dh ** 0.5
+    sees = torch.ones(L, L, dtype=torch.bool).tril() if causal else torch.ones(L, L, dtype=torch.bool)
+    got = torch.where(sees, torch.exp(s - lse[..., None]), torch.zeros_like(s))
+    assert (got - p).abs().max() <= 1e-14
+    assert (torch.where(sees, torch.exp(s), torch.zeros_like(s)).sum(-1).log() - lse).abs().max() <= 1e-12
+    assert (p.sum(-1) - 1.0).abs().max() <= 1e-14
+    if causal:
+        assert torch.equal(lse[:, :, 0], s[:, :, 0, 0])                   # row 0 sees one key
+
+
+def _row_keep(seed, ctr, L, p):
+    """one row of the drawn mask at an explicit 64-bit counter, word by word"""
+    from tests import counter_rng
+    assert 0 <= ctr < 2 ** 64
+    out = np.zeros(L, dtype=bool)
+    for j in range(L):
+        w = counter_rng.rng4(np.uint64(ctr), np.uint32(j // 4), seed).reshape(4)
+        out[j] = counter_rng.u01(w[j % 4]) >= np.float32(p)
+    return out
+
+
+@pytest.mark.parametrize("ref_name", ["sasrec_ref", "bert4rec_ref"])
+def test_drawn_keep_mask_carries_into_the_high_counter_word(ref_name):
+    """counter 2^32 - 5 with B H L = 24 rows: rows 0..4 sit below the carry, rows 5.. at 2^32 + (row - 5); each equals the
+    single-row draw at its explicit 64-bit counter, and a counter cut to 32 bits would draw something else"""
+    import importlib
+    ref = importlib.import_module(f"tests.{ref_name}")
+    seed, base, p = 0xA5C319E75DEECE66, 2 ** 32 - 5, 0.2
+    B, H, L = 2, 3, 4
+    keep = ref.attn_keep_drawn(seed, base, B, H, L, p).reshape(B * H * L, L)
+    for r in range(B * H * L):
+        ctr = base + r
+        assert (ctr >= 2 ** 32) == (r >= 5)
+        assert np.array_equal(keep[r], _row_keep(seed, ctr, L, p)), r
+    wide = ref.attn_keep_drawn(seed, base, 2, 1, 63, p).reshape(126, 63)
+    after = np.stack([_row_keep(seed, base + r, 63, p) for r in (4, 5, 6, 125)])
+    assert np.array_equal(wide[[4, 5, 6, 125]], after)
+    cut = np.stack([_row_keep(seed, (base + r) & 0xFFFFFFFF, 63, p) for r in (5, 6, 125)])
+    assert not np.array_equal(wide[[5, 6, 125]], cut)
+
+
+@pytest.mark.parametrize("L", [1, 2, 17, 49, 63])
+def test_drawn_keep_mask_at_lengths_off_the_float4(L):
+    """L not a multiple of 4: the last float4 of a row is drawn whole and cut; column j is still word j % 4 of float4 j / 4,
+    and a row's columns do not depend on L"""
+    from tests import bert4rec_ref
+    seed, base, p = 0x5DEECE66D1234, (1 << 33) + 7, 0.2
+    B, H = 2, 2
+    for ref in (sasrec_ref, bert4rec_ref):
+        keep = ref.attn_keep_drawn(seed, base, B, H, L, p)
+        assert keep.shape == (B, H, L, L) and keep.dtype == bool
+        flat = keep.reshape(B * H * L, L)
+        for r in sorted({0, L // 2, B * H * L - 1}):
+            assert np.array_equal(flat[r], _row_keep(seed, base + r, L, p)), r
+            assert np.array_equal(flat[r], _row_keep(seed, base + r, 64, p)[:L]), r
+    if L >= 17:
+        assert abs(1.0 - keep.mean() - p) < 0.05
+
+
+def test_edge_case_inputs_have_the_properties_their_tests_rely_on():
+    from tests import seq_attn_ref, test_gpu_bert4rec, test_gpu_sasrec
+    # the shape lists of the two parametrised float64 tests: a near-one-hot row at every L >= 7, the appended shapes included
+    for mod in (test_gpu_sasrec, test_gpu_bert4rec):
+        assert {(2, 32, 4, 32), (2, 48, 1, 32)} <= set(mod.ATTN_SHAPES)
+        for shape in mod.ATTN_SHAPES:
+            if shape[0] <= 5 and shape[1] >= 7:
+                for masked in (False, True):
+                    c = mod.attn_case(shape, masked)
+                    assert c["peak"] > 0.99, (mod.__name__, shape, masked)
+                    assert c["lse"].shape == (shape[0], shape[2], shape[1])
+    # the drawn-route cases: every L once per flavour, every head layout at two or more L, one of them off the tile
+    for flavour in seq_attn_ref.FLAVOURS:
+        shapes = seq_attn_ref.drawn_shapes(flavour)
+        assert sorted(s[1] for s in shapes) == list(seq_attn_ref.EDGE_L) and {s[0] for s in shapes} == {2, 3}
+        for heads in seq_attn_ref.EDGE_HEADS:
+            at = [s[1] for s in shapes if s[2:] == heads]
+            assert len(at) >= 2 and any(L % 16 for L in at), (flavour, heads, at)
+            assert heads[0] * heads[1] <= 128
+    assert seq_attn_ref.SEED >> 32 and seq_attn_ref.SEED < 2 ** 64
+    # the range case: the even rows' logits overflow an unshifted float32 exp, and the ordinary rows alone keep gq and gk
+    # of ordinary size, so a relative bound on them means something
+    for flavour in seq_attn_ref.FLAVOURS:
+        c = seq_attn_ref.range_case(flavour)
+        assert 80.0 < c["logit_std_even"] < 125.0 and c["logit_max"] > 200.0
+        for name in ("gq", "gk"):
+            assert float(c["ordinary"][name].abs().max()) > 1.0, (flavour, name)
+            assert float(c["ref"][name].abs().max()) > 1.0, (flavour, name)
+        assert all(torch.isfinite(c["ref"][n]).all() for n in c["ref"])
+    # the keep-mask edges: the dropped row and column are what the reference says they are
+    for flavour in seq_attn_ref.FLAVOURS:
+        for shape in seq_attn_ref.KEEP_EDGE_SHAPES:
+            c = seq_attn_ref.keep_edge_case(flavour, shape)
+            assert not c["keep"][:, :, c["row"]].any() and not c["keep"][:, :, :, c["col"]].any()
+            assert c["keep"].mean() > 0.6 and 0 < c["col"] < c["row"] == shape[1] - 1
+            assert not c["ref"]["out"][:, c["row"]].any() and not c["ref"]["gq"][:, c["row"]].any()
+            assert not c["ref"]["gv"][:, c["col"]].any() and c["ref"]["gv"][:, c["col"] + 1].any()
+    # the BCE widths: logits of standard deviation ~24 at every width (3 or 5 rows alone need not reach 30; together they do)
+    assert len(seq_attn_ref.BCE_EDGE_CASES) == 21
+    small = [seq_attn_ref.bce_edge_case(R, d) for R, d in seq_attn_ref.BCE_EDGE_CASES if R <= 5]
+    logits = torch.cat([torch.cat([c["xp"], c["xn"]]) for c in small])
+    assert 18.0 < float(logits.std()) < 30.0 and float(logits.max()) > 30.0 and float(logits.min()) < -30.0
+    for R, d in seq_attn_ref.BCE_EDGE_CASES:
+        c = seq_attn_ref.bce_edge_case(R, d)
+        if R >= 255:
+            assert c["span"] > 30.0
+        assert c["grows"].shape == (2 * R, d) and not c["grows"][:R][~c["valid"]].any()
+        # the per-row gradients scatter to the table gradient
+        gt = torch.zeros_like(c["gt"]).index_add_(0, torch.cat([c["pos"], c["neg"]]), c["grows"])
+        assert (gt - c["gt"]).abs().max() <= 1e-12 * max(1.0, float(c["gt"].abs().max()))
+    c = seq_attn_ref.bce_bad_id_case()
+    assert int(c["usable"].sum()) == 7 and not c["gh"][~c["usable"]].any() and c["gh"][c["usable"]].any(dim=1).all()
