@@ -983,6 +983,47 @@ srh_status_t srh_rows_live_sum_f32(const srh_live_sum_problem_t* problems, int32
                                    void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * (a-19) SEPT -- tf.math.l2_normalize(x, axis=1) after every propagation of the four encoders (model/graph/SEPT.py:48-64)
+ * and the tri-training step label_prediction -> top_k -> neighbor_discrimination (SEPT.py:98-134).
+ *
+ * srh_rows_l2norm_fwd_f32: inv_r = rsqrt(max(sum_c y_rc^2, 1e-12)), out_r = y_r * inv_r; d_out (n x d) and d_inv (n) are
+ *   WRITTEN.  srh_rows_l2norm_bwd_f32: gy_r = (g_r - out_r (out_r . g_r)) * inv_r where the squared norm was >= 1e-12,
+ *   g_r * 1e6 below it (decided from inv_r == 1e6).  Any 1 <= d <= 256 (else SRH_ERR_UNSUPPORTED), any n >= 0; one wave per
+ *   row, no atomics, the same bits on every call.
+ * srh_tri_nd_fwd_bwd: views V0 (friend), V1 (sharing), V2 (rec) and A (aug), each n x d: the gathered rows of the batch's
+ *   unique users, un-normalised.  v = normalize(V), a = normalize(A) under the rule above;
+ *     s_v[i][j] = v_i . a_j,  p_v[i][j] = softmax_j(s_v[i][.])            (temperature 1, the diagonal included)
+ *     pos_v[i]  = the k largest j of p_a[i][j] + p_b[i][j], (a, b) the two views other than v; value descending, ties
+ *                 to the lowest j (tf.math.top_k; the reference's halving of the sum is exact and monotone)
+ *     d_loss[v] = loss_scale * sum_i [ log sum_j e_v[i][j] - log sum_{j in pos_v[i]} e_v[i][j] ],  e = exp(s / tau)
+ *     dL/ds_v[i][j] = loss_scale / tau * ( e_ij / sum_j e_ij - [j in pos_v[i]] e_ij / sum_{j in pos} e_ij )
+ *   The indices carry no gradient.  d_loss (double[3]), d_gview[v] and d_gaug (n x d, the normalisation backward
+ *   included) and d_pos (int32, 3 x n x k, best first) are WRITTEN.  No n x n matrix reaches memory (the positives travel
+ *   between the passes as n bits per row); exponentials are taken as exp((s - 1) / .); every product runs on the f32
+ *   MFMA; no float atomics: the same bits on every call.  The ranking key of (i, j) depends on rows i and j alone, so
+ *   identical aug rows tie exactly.  d = 64 or 128 (zero-pad narrower rows), 1 <= k <= 32, n >= k: anything else is
+ *   SRH_ERR_UNSUPPORTED with a message.  d_ws >= srh_tri_nd_ws_bytes(n, d, k) (0 for an unsupported shape).
+ * ---------------------------------------------------------------------------------- */
+srh_status_t srh_rows_l2norm_fwd_f32(const float* d_y, int64_t n, int32_t d, float* d_out, float* d_inv, void* stream);
+srh_status_t srh_rows_l2norm_bwd_f32(const float* d_g, const float* d_out, const float* d_inv, int64_t n, int32_t d,
+                                     float* d_gy, void* stream);
+typedef struct srh_tri_nd_args {
+  const float* d_view[3];
+  const float* d_aug;
+  int64_t n;
+  int32_t d;
+  int32_t k;
+  float tau;
+  float loss_scale;
+  double* d_loss;
+  float* d_gview[3];
+  float* d_gaug;
+  int32_t* d_pos;
+} srh_tri_nd_args_t;
+int64_t srh_tri_nd_ws_bytes(int64_t n, int32_t d, int32_t k);
+srh_status_t srh_tri_nd_fwd_bwd(const srh_tri_nd_args_t* args, void* d_ws, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * (f-1) Dataset files -> id arrays -- replaces the python loops of data/loader.py:22-33
  * (FileIO.load_data_set: one "user item weight" line per interaction, single-space separated)
  * and data/ui_graph.py:29-45 (ids in first-appearance order of the training file; test pairs kept

@@ -14,6 +14,8 @@ class SELFRec:
         self.training_data = FileIO.open_data_set(config['training.set'], kind)
         self.test_data = FileIO.open_data_set(config['test.set'], kind)
         self.kwargs = {}
+        if config.contain('social.data'):          # SELFRec.py:13-15: SEPT's (and MHCN's) trust pairs
+            self.kwargs['social.data'] = FileIO.load_social_data(config['social.data'])
         print('Reading data and preprocessing...')
 
     def execute(self):

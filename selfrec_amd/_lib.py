@@ -70,7 +70,14 @@ class LiveSumProblem(C.Structure):
                 ("rng_seed", C.c_uint64), ("rng_counter", C.c_uint64)]
 
 
-SCALAR_WS_BYTES = 64         # SRH_SCALAR_WS_BYTES
+class TriNdArgs(C.Structure):
+    """struct srh_tri_nd_args (include/selfrec_hip.h)."""
+    _fields_ = [("d_view", C.c_void_p * 3), ("d_aug", C.c_void_p), ("n", C.c_int64), ("d", C.c_int32), ("k", C.c_int32),
+                ("tau", C.c_float), ("loss_scale", C.c_float), ("d_loss", C.c_void_p), ("d_gview", C.c_void_p * 3),
+                ("d_gaug", C.c_void_p), ("d_pos", C.c_void_p)]
+
+
+SCALAR_WS_BYTES = 64        # SRH_SCALAR_WS_BYTES
 
 
 class BatchSegments(C.Structure):
@@ -201,6 +208,10 @@ SIGNATURES = {
     "srh_seq_embed_fwd_f32": (_i32, [_vp, _i64, _vp, _i64, _vp, _vp, _i64, _i32, _f32, _vp, _u64, _u64, _f32, _vp, _vp]),
     "srh_rows_live_sum_ws_bytes": (_i64, [C.POINTER(LiveSumProblem), _i32, _i32]),
     "srh_rows_live_sum_f32": (_i32, [C.POINTER(LiveSumProblem), _i32, _i32, _vp, _vp]),
+    "srh_rows_l2norm_fwd_f32": (_i32, [_vp, _i64, _i32, _vp, _vp, _vp]),
+    "srh_rows_l2norm_bwd_f32": (_i32, [_vp, _vp, _vp, _i64, _i32, _vp, _vp]),
+    "srh_tri_nd_ws_bytes": (_i64, [_i64, _i32, _i32]),
+    "srh_tri_nd_fwd_bwd": (_i32, [C.POINTER(TriNdArgs), _vp, _vp]),
     "srh_adam_step": (_i32, [_vp, _vp, _vp, _vp, _i64, _i64, _vp, _f32, _f32, _f32, _f32, _vp]),
     "srh_adam_step_reset": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _vp, _f32, _f32, _f32, _f32, _vp, _i32, _vp, _vp, _vp]),
     "srh_score_mask_topk": (_i32, [_vp, _vp, _i64, _vp, _i64, _i32, _vp, _vp, _i32, _vp, _i64, _vp, _vp, _vp]),

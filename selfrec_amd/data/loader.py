@@ -103,6 +103,18 @@ class FileIO:
         return FileIO.load_data_set(file, rec_type)
 
     @staticmethod
+    def load_social_data(file):
+        """reference data/loader.py:53-66: every line -> [user1, user2, weight]; the weight is 1 when the line has fewer
+        than three fields"""
+        print('loading social data...')
+        social_data = []
+        with open(file) as src:
+            for raw in src:
+                parts = raw.strip().split(' ')
+                social_data.append([parts[0], parts[1], 1 if len(parts) < 3 else float(parts[2])])
+        return social_data
+
+    @staticmethod
     def write_file(dir, file, content, op='w'):
         os.makedirs(dir, exist_ok=True)
         with open(dir + file, op) as dst:

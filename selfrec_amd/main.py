@@ -4,10 +4,11 @@
     python -m selfrec_amd.main SASRec --synthetic beauty-seq
     python -m selfrec_amd.main BERT4Rec --synthetic beauty-seq
     python -m selfrec_amd.main CL4SRec --synthetic beauty-seq
+    python -m selfrec_amd.main SEPT --synthetic douban-book
 
 ``--synthetic SHAPE`` writes a generated dataset of that shape (selfrec_amd/synth.py) to the
 paths the config names, if they do not exist yet -- the reference's dataset files are not
-redistributable.
+redistributable.  A config that names a ``social.data`` file (SEPT) gets a generated trust file the same way.
 """
 import argparse
 import os
@@ -17,7 +18,7 @@ from . import synth
 from .SELFRec import SELFRec
 from .util.conf import ModelConf
 
-MODELS = ['MF', 'LightGCN', 'XSimGCL', 'SimGCL', 'SGL', 'DirectAU', 'MixGCF', 'BUIR', 'SelfCF', 'NCL', 'UserKNN', 'ItemKNN', 'SSL4Rec', 'SASRec', 'BERT4Rec', 'CL4SRec']
+MODELS = ['MF', 'LightGCN', 'XSimGCL', 'SimGCL', 'SGL', 'DirectAU', 'MixGCF', 'BUIR', 'SelfCF', 'NCL', 'UserKNN', 'ItemKNN', 'SSL4Rec', 'SASRec', 'BERT4Rec', 'CL4SRec', 'SEPT']
 
 
 def main(argv=None):
@@ -41,6 +42,11 @@ def main(argv=None):
             tu, ti, su, si, _, _ = synth.make_dataset(args.synthetic)
             synth.write_text(conf['training.set'], tu, ti)
             synth.write_text(conf['test.set'], su, si)
+    if args.synthetic and conf.contain('social.data') and not os.path.exists(conf['social.data']):
+        if args.synthetic not in synth.SHAPES:
+            ap.error(f"a graph model takes one of {sorted(synth.SHAPES)}")
+        os.makedirs(os.path.dirname(conf['social.data']) or '.', exist_ok=True)
+        synth.write_social(conf['social.data'], synth.make_social(args.synthetic))
     t0 = time.time()
     SELFRec(conf).execute()
     print(f"Running time: {time.time() - t0:.2f} s")

@@ -110,6 +110,45 @@ def write_text(path: str, users: np.ndarray, items: np.ndarray, weight: int = 1)
         f.writelines(f"{a} {b} {weight}\n" for a, b in zip(users.tolist(), items.tolist()))
 
 
+# ---- social relations (conf key social.data: SEPT) ---------------------------------------------------------------------
+def make_social(shape: str = "tiny", seed: int = 2024, mean_degree: float = 12.6, reciprocal: float = 0.3,
+                closure: float = 0.25):
+    """Seeded directed trust pairs over the users of ``shape`` in the loader's in-memory format ``[[u, v, 1], ...]``
+    (reference data/loader.py:53-66), user names as make_dataset / as_triples write them.
+
+    Out-degrees are skewed (a capped Pareto tail whose mean is near douban-book's 12.6 trust lines per user), followees
+    are drawn from a Zipf popularity, a share ``reciprocal`` of the pairs is followed back, and for a share ``closure`` of
+    the pairs u -> v the user u also follows one of v's followees -- triangles, without which SEPT's friend view
+    (S.S) (.) S would be empty.  No self-pairs, no duplicates, file order shuffled."""
+    n = SHAPES[shape][0]
+    rng = np.random.default_rng(seed + 7)
+    cap = max(1, min(n - 1, 2000))
+    scale = mean_degree / 3.0 / (1.0 + reciprocal + 0.6 * closure)          # E[pareto(1.5) + 1] = 3; the added pairs
+    deg = np.minimum(np.floor((rng.pareto(1.5, n) + 1.0) * scale).astype(np.int64), cap)
+    cu = np.cumsum(_zipf_weights(n, 0.8, rng))
+    cu[-1] = 1.0
+    src = np.repeat(np.arange(n, dtype=np.int64), deg)
+    dst = np.searchsorted(cu, rng.random(src.size), side="right").astype(np.int64)
+    keys = np.unique(src[src != dst] * n + dst[src != dst])
+    src, dst = keys // n, keys % n
+    back = rng.random(keys.size) < reciprocal
+    # u -> v, v -> w  =>  u -> w for a share of the pairs (keys are sorted by source: a CSR without building one)
+    indptr = np.searchsorted(src, np.arange(n + 1))
+    out_deg = np.diff(indptr)
+    close = (rng.random(keys.size) < closure) & (out_deg[dst] > 0)
+    w = dst[indptr[dst[close]] + np.floor(rng.random(int(close.sum())) * out_deg[dst[close]]).astype(np.int64)]
+    u = src[close]
+    keys = np.unique(np.concatenate([keys, dst[back] * n + src[back], u[u != w] * n + w[u != w]]))
+    keys = keys[rng.permutation(keys.size)]
+    return [[a, b, 1] for a, b in zip((keys // n).astype(str).tolist(), (keys % n).astype(str).tolist())]
+
+
+def write_social(path: str, lines) -> None:
+    """``"user1 user2 weight"`` lines, the format FileIO.load_social_data reads."""
+    with open(path, "w") as f:
+        f.writelines(f"{a} {b} {w}\n" for a, b, w in lines)
+
+
 # ---- sequence datasets (model.type: sequential) -----------------------------------------------------------------------
 # name -> (n_sequences, n_items, n_interactions_total)   [train + the one held-out item per sequence]
 SEQ_SHAPES = {
