@@ -730,6 +730,15 @@ srh_status_t srh_allreduce_sum_f32(float* d_buf, int64_t n_elem, void* comm, voi
  * the positive row of each query in T (may repeat).  The B x N logits are never materialised;
  * exponentials are taken as exp((s - 1) / tau) (unit rows: no running max needed).  Both
  * products of both passes run on the f32 MFMA.  No float atomics: the same bits on every call.
+ * ENVELOPE: exp((s - 1) / tau) cannot overflow, but in f32 it is subnormal below cos = 1 - 87 tau
+ * and 0 below 1 - 103 tau, where the reference's exp(s / tau) is still accurate.  Any data is safe
+ * for tau >= 0.023 (exp(-2 / tau) is normal).  Below that, a query with no key above
+ * cos = 1 - 87 tau has no usable row sum: when the sum is under N * 2^-130 (the subnormal terms'
+ * errors of 2^-150 each may then exceed 2^-20 of it) that query's loss term is NaN, and so is
+ * d_loss[0]; its gradient rows are not meaningful.  An idx outside [0, N) reads nothing and
+ * makes the loss NaN as well; the d_gq rows of the other queries are unaffected by either.
+ * Rows of norm below 1e-12 (zero rows included) follow F.normalize's clamp: x / 1e-12 forward,
+ * g / 1e-12 backward.
  * Outputs are WRITTEN: d_loss[0] = loss_scale * loss (double), d_gq (B x d) = loss_scale *
  * dL/dQ, d_gt (N x d, dense) = loss_scale * dL/dT.  d = 64 or 128 (zero-pad narrower rows).
  * d_ws >= the SUM over problems of srh_table_nce_ws_bytes(B, N, d).  `problems` is a HOST
@@ -827,6 +836,8 @@ srh_status_t srh_knn_score_topk(int32_t mode, const int32_t* d_users, int64_t n_
  * srh_batch_softmax_fwd_bwd: u = normalize(U), v = normalize(V) (B x d each), p_b = exp(u_b.v_b / tau) / sum_j
  *   exp(u_b.v_j / tau);  *d_loss = mean_b -log(p_b + 1e-5) (double), d_gu / d_gv its gradients w.r.t. U and V (written).
  *   The B x B logits are never materialised.  d = 64 or 128; d_ws >= srh_batch_softmax_ws_bytes(B, d).
+ *   The same envelope as srh_table_nce_fwd_bwd (a-12): exponentials are exp((s - 1) / tau) in f32; any data is safe for
+ *   tau >= 0.023; below that, a row u_b with no v_j above cos = 1 - 87 tau (row sum under B * 2^-130) makes *d_loss NaN.
  * ---------------------------------------------------------------------------------- */
 typedef struct srh_tower_weights {
   const float* d_w1; /* (1024, 64) */

@@ -10,7 +10,9 @@
 //     loss = mean_b -log(p_b + 1e-5), p_b = P_bb                      dL/ds_bj = w_b (P_bj - [j == b]) / (B tau)
 //     with w_b = p_b / (p_b + 1e-5): InfoNCE's row gradient scaled by w_b.
 // The B x N logits are never materialised.  The rows are unit vectors, so every logit is <= 1/tau and the exponentials
-// are taken as exp((s - 1) / tau): no running max.
+// are taken as exp((s - 1) / tau): no running max.  That cannot overflow, but it underflows where the reference's exp(s / tau)
+// does not: a query with no key above cos = 1 - 87 tau has a row sum of subnormal terms (0 below 1 - 103 tau), and the finish
+// makes its loss term NaN (rowsum < N 2^-130).  For tau >= 0.023 no data can get there.
 //   prep    normalise Q and T into the workspace (rows and their norms)
 //   pass 1  query tiles x key chunks: per query and chunk, sum_j e_bj and sum_j e_bj t_j (e = exp((s - 1)/tau))
 //   finish  per query: the chunk partials in chunk order -> row sum, loss term, dL/dQ (normalisation backward fused),
@@ -303,19 +305,24 @@ __global__ __launch_bounds__(256) void ct_finish(CtArgs a) {
   const float spos = srh::group_sum<LPR>(srh::f4_dot(q, t));
   const float inv_rs = (float)(1.0 / rs);
   const float inv_tau = a.inv_tau;
+  // The terms are exp((s - 1)/tau) in f32: below cos = 1 - 87 tau they are subnormal, each off by up to 2^-150, and below
+  // 1 - 103 tau they are 0.  Under N 2^-130 the N terms' errors may be more than 2^-20 of the row sum (or all of it, at
+  // rowsum = 0): such a row's loss term is NaN, like that of an index outside the table.  No data reaches this for
+  // tau >= 0.023 (exp(-2/tau) is normal).
+  const bool rs_ok = !(rs < (double)P.N * 0x1p-130);
   // dL/dq_b = k (O_b / rowsum - t_pos(b))
   float k = P.gscale;
   if (SOFTMAX) {
     const double p = exp(((double)spos - 1.0) * (double)inv_tau) / rs;
     const double w = p / (p + kBsEps);
     if (lane == 0) {
-      P.row_loss[b] = -log(p + kBsEps);
+      P.row_loss[b] = rs_ok ? -log(p + kBsEps) : (double)NAN;
       P.cw[b] = (float)(w / rs);
       P.cd[b] = (float)w;
     }
     k = (float)w * inv_tau / (float)P.B;
   } else if (lane == 0) {
-    P.row_loss[b] = jok ? (double)inv_tau * (1.0 - (double)spos) + log(rs) : (double)NAN;
+    P.row_loss[b] = jok && rs_ok ? (double)inv_tau * (1.0 - (double)spos) + log(rs) : (double)NAN;
     P.cw[b] = inv_rs;
     P.cd[b] = 1.f;
   }
