@@ -819,7 +819,9 @@ srh_status_t srh_knn_score_topk(int32_t mode, const int32_t* d_users, int64_t n_
  * item_tower: Linear(64, 1024) -> ReLU -> Linear(1024, 128) -> Tanh) and util/loss_torch.py:25-32 (batch_softmax_loss).
  *
  * srh_tower_fwd_f32: out (n x 128) = tanh(W2 relu(W1 x_r + b1) + b2) for rows x_r = d_table[d_idx[r]] (d_table[r] when
- *   d_idx is NULL; an id outside [0, n_table) reads a zero row).  Rows r >= mask_row0 take feature dropout: x * m with
+ *   d_idx is NULL; an id outside [0, n_table) reads a zero row: exact zeros in d_x_out, masked or not, and the row's output
+ *   is the tower's value at zero).  relu is max(z, 0) with relu'(0) = 0, as torch: a unit whose pre-activation is exactly 0
+ *   writes 0 to d_hidden and passes no gradient.  Rows r >= mask_row0 take feature dropout: x * m with
  *   m = keep ? 1 / (1 - drop_p) : 0 (nn.Dropout's scaled mask).  keep[r][c] is d_mask_in[(r - mask_row0) * 64 + c] != 0
  *   when d_mask_in is given, else it is drawn from the counter RNG of the SpMM epilogue (tests/counter_rng.py): the word
  *   of column c in float4 c / 4 at counter rng_counter + (r - mask_row0), keep = u01(word) >= drop_p -- a pure function
@@ -828,11 +830,16 @@ srh_status_t srh_knn_score_topk(int32_t mode, const int32_t* d_users, int64_t n_
  *   what srh_tower_bwd_f32 reads.  The weights are nn.Linear's: W1 (1024 x 64), W2 (128 x 1024) row-major.
  * srh_tower_bwd_f32: from the forward's x, hidden and out and the upstream d_gy (n x 128): d_gx (n x 64, the gradient
  *   w.r.t. the gathered rows before dropout: already multiplied by the mask of rows >= mask_row0 when d_mask is given),
- *   d_gw1, d_gb1, d_gw2, d_gb2 (written, not added).  Reductions over rows in a fixed order, no float atomics: the same
- *   bits on every call.  d_ws >= srh_tower_bwd_ws_bytes(n).
+ *   d_gw1, d_gb1, d_gw2, d_gb2 (written, not added).  A unit is alive where d_hidden > 0 and nowhere else: the rows of
+ *   d_gw1 and the entries of d_gb1 of a unit that is dead on every row are exact zeros.  The row of d_gx of an id outside
+ *   the table is the gradient w.r.t. the zero row read there (not zero); srh_rows_segment_sum_f32 hands it to no table row.
+ *   Reductions over rows in a fixed order, no float atomics: the same bits on every call.  d_ws >= srh_tower_bwd_ws_bytes(n).
  * srh_rows_segment_sum_f32: d_out[d_seg_row[s]] += sum of rows d_order[d_seg_start[s] .. d_seg_start[s + 1]) of d_x
  *   (n_rows x d), in that order: the deterministic scatter-add of gathered-row gradients into a table (the segments are
- *   a stable sort of the row ids; each table row at most once).
+ *   a stable sort of the row ids; each table row at most once).  Per segment and column the terms are added in float32 from
+ *   0 in that order and the sum is then ADDED to what d_out holds; rows of d_out that no segment names are not touched.  A
+ *   d_seg_row entry outside [0, n_table) skips its segment, a d_order entry outside [0, n_rows) its term; n_seg = 0 returns
+ *   at once.
  * srh_batch_softmax_fwd_bwd: u = normalize(U), v = normalize(V) (B x d each), p_b = exp(u_b.v_b / tau) / sum_j
  *   exp(u_b.v_j / tau);  *d_loss = mean_b -log(p_b + 1e-5) (double), d_gu / d_gv its gradients w.r.t. U and V (written).
  *   The B x B logits are never materialised.  d = 64 or 128; d_ws >= srh_batch_softmax_ws_bytes(B, d).

@@ -1362,6 +1362,8 @@ def rows_segment_sum(x, plan, out):
     n_rows, d = int(x.shape[0]), int(x.shape[1])
     if int(order.numel()) != n_rows or int(out.shape[1]) != d:
         raise SelfrecHipError("rows_segment_sum: the plan and the tables do not match")
+    if int(seg_row.numel()) == 0:          # no segments: nothing to add (an empty tensor has no address to hand over)
+        return out
     check(_lib.load().srh_rows_segment_sum_f32(_p(x.contiguous(), torch.float32, "x"), n_rows, d,
                                                _p(order, torch.int32, "order"), _p(seg_start, torch.int32, "seg_start"),
                                                _p(seg_row, torch.int32, "seg_row"), int(seg_row.numel()),
