@@ -22,8 +22,6 @@ What runs where:
 
 Stated deviations from the reference: ``torch.optim.Adam`` adds eps to sqrt(v_hat) where TF1's AdamOptimizer adds it to
 sqrt(v) before the bias correction; the initial tables come from torch's RNG (xavier_uniform_), not TF's."""
-import os
-
 import numpy as np
 import torch
 import torch.nn as nn
@@ -33,30 +31,21 @@ from ... import ops
 from ...base.torch_interface import TorchGraphInterface
 from ...data.augmentor import GraphAugmentor
 from ...data.social import Relation
+from ...util.route import route
 from ._oplevel import OpLevelRecommender
 
 TAU = 0.1                             # SEPT.py:131-132
 PAIRS = ((1, 2), (0, 2), (0, 1))      # SEPT.py:145-147: the two views that label friend / sharing / rec
 
 
-def _route(env, key, conf):
-    route = os.environ.get(env)
-    if route is None and conf is not None and conf.contain(key):
-        route = conf[key]
-    route = 'hip' if route is None else str(route).strip().lower()
-    if route not in ('hip', 'torch'):
-        raise ValueError(f"{key} / {env}: {route!r} is neither 'hip' nor 'torch'")
-    return route
-
-
 def nd_route(conf=None):
     """'hip' or 'torch': SRH_SEPT_ND, else the conf's engine.nd, else the kernels"""
-    return _route('SRH_SEPT_ND', 'engine.nd', conf)
+    return route('SRH_SEPT_ND', 'engine.nd', conf)
 
 
 def norm_route(conf=None):
     """'hip' or 'torch': SRH_SEPT_NORM, else the conf's engine.norm, else the kernels"""
-    return _route('SRH_SEPT_NORM', 'engine.norm', conf)
+    return route('SRH_SEPT_NORM', 'engine.norm', conf)
 
 
 def l2_normalize(x):

@@ -8,8 +8,8 @@ What runs where:
     three calls' in exact arithmetic.  ``three`` is the reference's three calls, the A/B partner.
   * ``engine.embed: hip`` (default; ``SRH_CL4SREC_EMBED``) takes the embedding front -- both gathers, scale, sum, dropout,
     padding mask -- as one launch (ops.SeqEmbedFn) whose two table gradients, like the BCE's (ops.SeqBceLiveFn), are summed
-    over the LIVE rows only in chunks of fixed length (srh_rows_live_sum_f32).  ``torch`` is SASRec_Model.forward's front
-    (ops.GatherRowsFn twice, mul, add, dropout, mask) and ops.SeqBceFn: the parent's route.
+    over the LIVE rows only in chunks of fixed length (srh_rows_live_sum_f32).  ``torch`` is the front SASRec takes
+    (ops.GatherRowsFn twice, mul, add, dropout, mask) and ops.SeqBceFn.  Both fronts are encoder.SeqEncoder.front.
   * ``engine.attention`` as in SASRec; the InfoNCE of the two (B, d) row sets is ops.InfoNceFn (util.loss_torch.InfoNCE for
     a width that entry does not take).  A model on the CPU takes torch's expressions throughout.
 
@@ -17,9 +17,7 @@ The item table has item_num + 2 rows (item_num + 1: the mask token) and is creat
 reference replaces it, so ``torch.manual_seed`` reproduces its initial weights and the state_dict order.
 
 Host work of a step: ``StagedViews`` turns the stacked ids and positions, y, neg, the last-row indices of both views and
-every plan the routes need into ONE int32 upload."""
-import os
-
+every plan the routes need into ONE int32 upload (encoder.upload_with_plans), cut into one encoder.Group per pass."""
 import numpy as np
 import torch
 import torch.nn as nn
@@ -28,33 +26,20 @@ from ... import ops
 from ...base.seq_recommender import SequentialRecommender
 from ...data.augmentor import SequenceAugmentor
 from ...util.loss_torch import InfoNCE, l2_reg_loss
+from ...util.route import route
 from ...util.sampler import next_batch_sequence
-from .SASRec import SASRec, SASRec_Model, attention_route
-
-
-def _route(env, key, conf, choices):
-    route = os.environ.get(env)
-    if route is None and conf is not None and conf.contain(key):
-        route = conf[key]
-    route = choices[0] if route is None else str(route).strip().lower()
-    if route not in choices:
-        raise ValueError(f"{key} / {env}: {route!r} is neither {choices[0]!r} nor {choices[1]!r}")
-    return route
+from .encoder import Group, LastRowScores, upload_with_plans
+from .SASRec import SASRec_Model, attention_route
 
 
 def views_route(conf=None):
     """'one' or 'three': SRH_CL4SREC_VIEWS, else the conf's engine.views, else one stacked encoder pass"""
-    return _route('SRH_CL4SREC_VIEWS', 'engine.views', conf, ('one', 'three'))
+    return route('SRH_CL4SREC_VIEWS', 'engine.views', conf, ('one', 'three'))
 
 
 def embed_route(conf=None):
     """'hip' or 'torch': SRH_CL4SREC_EMBED, else the conf's engine.embed, else the kernels"""
-    return _route('SRH_CL4SREC_EMBED', 'engine.embed', conf, ('hip', 'torch'))
-
-
-class _Group:
-    """one encoder pass of a StagedViews: ids, positions, the padding mask and the two plans of its gathers"""
-    __slots__ = ('shape', 'seq', 'pos', 'plans', 'live')
+    return route('SRH_CL4SREC_EMBED', 'engine.embed', conf)
 
 
 class StagedViews:
@@ -88,30 +73,17 @@ class StagedViews:
         yn = np.concatenate([y, neg])
         plans.append(ops.live_plan_host(yn, np.concatenate([valid, valid])) if hip else ops.scatter_plan_host(yn))
         head = [seq_all, pos_all, y, neg, lasts[0], lasts[1]]
-        parts = [np.ascontiguousarray(a, dtype=np.int32) for a in head] + [a for plan in plans for a in plan]
-        flat = torch.from_numpy(np.concatenate(parts)).to(device)
-        cut, at = [], 0
-        for a in parts:
-            cut.append(flat[at:at + a.size])
-            at += a.size
+        cut, dev_plans = upload_with_plans(head, plans, device)
         self.y, self.neg, self.last = cut[2], cut[3], (cut[4], cut[5])
-        width = 5 if hip else 3
-        dev_plans = [tuple(cut[len(head) + width * k:len(head) + width * (k + 1)]) for k in range(len(plans))]
-        self.groups = []
-        for k, (lo, hi) in enumerate(bounds):
-            g = _Group()
-            g.shape = ((hi - lo) // L, L)
-            g.seq, g.pos = cut[0][lo:hi], cut[1][lo:hi]
-            g.plans = (dev_plans[2 * k], dev_plans[2 * k + 1])
-            g.live = (g.seq != 0).reshape(*g.shape, 1)
-            self.groups.append(g)
+        self.groups = [Group(((hi - lo) // L, L), cut[0][lo:hi], cut[1][lo:hi], dev_plans[2 * k:2 * k + 2])
+                       for k, (lo, hi) in enumerate(bounds)]
         self.bce_plan = dev_plans[-1]
         self.valid = (cut[1][:per] != 0).to(torch.uint8)
         self.n_valid = int(np.count_nonzero(valid))
         self.live_share = float(np.count_nonzero(seq_all)) / seq_all.size
 
 
-class CL4SRec(SequentialRecommender):
+class CL4SRec(LastRowScores, SequentialRecommender):
     def __init__(self, conf, training_set, test_set):
         super(CL4SRec, self).__init__(conf, training_set, test_set)
         section = self.config['CL4SRec']
@@ -211,55 +183,12 @@ class CL4SRec(SequentialRecommender):
             fn, plan = ops.SeqBceFn, ops.scatter_plan(yn, dev)
         return fn.apply(hidden, table, ids[0], ids[1], ids[2].to(torch.uint8), int(np.count_nonzero(valid)), plan)
 
-    last_hidden = SASRec.last_hidden
-    item_table = SASRec.item_table
-    predict = SASRec.predict
-
 
 class CL4SRec_Model(SASRec_Model):
-    """SASRec_Model with the item_num + 2-row item table and a front that reads a StagedViews group"""
+    """SASRec_Model with an item table of item_num + 2 rows (item_num + 1: the mask token)"""
 
     def _init_model(self):
         super()._init_model()
         # the reference replaces the table once the network stands (CL4SRec.py:23-25): the same draws in the same order
-        self.item_emb = nn.Parameter(nn.init.xavier_uniform_(torch.empty(self.data.item_num + 2, self.emb_size)))
-
-    def uses_embed_kernel(self, staged):
-        return staged.route_embed == 'hip' and ops.seq_embed_supported(self.emb_size)
-
-    def forward(self, seq, pos, attn_keep=None, staged=None, group=0, emb_keep=None):
-        """(rows, L, d) hidden states.  Without ``staged`` (evaluation, a CPU model): SASRec_Model.forward on the id arrays.
-        With it: the encoder over staged.groups[group]; emb_keep: an optional (rows, L, d) keep mask of the embedding
-        dropout, replayed instead of drawn."""
-        if staged is None:
-            return super().forward(seq, pos, attn_keep)
-        g = staged.groups[group]
-        B, L = g.shape
-        d = self.emb_size
-        p = float(self.drop_rate) if self.training else 0.0
-        if self.uses_embed_kernel(staged):
-            seq_emb = ops.SeqEmbedFn.apply(self.item_emb, self.pos_emb, g.seq, g.pos, g.plans[0], g.plans[1], emb_keep, p,
-                                           self.rng_seed, self.rng_counter).reshape(B, L, d)
-            if emb_keep is None and p > 0.0:
-                self.rng_counter += B * L
-        else:
-            if staged.route_embed == 'hip':
-                raise ops.SelfrecHipError(f"engine.embed: hip serves widths {ops.SEQ_EMBED_WIDTHS}, not {d}")
-            items = ops.GatherRowsFn.apply(self.item_emb, g.seq, g.plans[0])
-            places = ops.GatherRowsFn.apply(self.pos_emb, g.pos, g.plans[1])
-            seq_emb = (items * d ** 0.5 + places).reshape(B, L, d)
-            if emb_keep is not None:
-                seq_emb = seq_emb * (emb_keep.reshape(B, L, d).to(seq_emb.dtype) / (1.0 - p))
-            else:
-                seq_emb = self.emb_dropout(seq_emb)
-            seq_emb = seq_emb * g.live
-        live = g.live
-        for i in range(len(self.attention_layers)):
-            normalized_emb = self.attention_layer_norms[i](seq_emb)
-            keep = None if attn_keep is None else attn_keep[i]
-            mha_outputs = self._attention(self.attention_layers[i], normalized_emb, seq_emb, keep)
-            seq_emb = normalized_emb + mha_outputs
-            seq_emb = self.forward_layer_norms[i](seq_emb)
-            seq_emb = self.forward_layers[i](seq_emb)
-            seq_emb = seq_emb * live
-        return self.last_layer_norm(seq_emb)
+        self.item_rows += 1
+        self.item_emb = nn.Parameter(nn.init.xavier_uniform_(torch.empty(self.item_rows, self.emb_size)))

@@ -6,6 +6,7 @@ addresses (``tensor.data_ptr()``) and the current HIP stream to libselfrec_hip.s
 from __future__ import annotations
 
 import ctypes as C
+import functools
 import random as _pyrandom
 
 import numpy as np
@@ -1515,45 +1516,35 @@ def seq_attn_full_bwd(q, k, v, lse, go, n_heads, *, keep=None, drop_p=0.0, rng_s
     return _seq_attn_bwd("srh_seq_attn_full_bwd_f32", q, k, v, lse, go, n_heads, keep, drop_p, rng_seed, rng_counter)
 
 
-class SeqAttnFn(torch.autograd.Function):
+class _SeqAttn(torch.autograd.Function):
+    """the fused attention core as one differentiable op of (q, k, v): causal (seq_attn_fwd / seq_attn_bwd) or over all
+    positions (seq_attn_full_fwd / seq_attn_full_bwd)"""
+
+    @staticmethod
+    def forward(ctx, causal, q, k, v, n_heads, keep, drop_p, rng_seed, rng_counter):
+        q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
+        ctx.fwd_bwd = (seq_attn_fwd, seq_attn_bwd) if causal else (seq_attn_full_fwd, seq_attn_full_bwd)
+        ctx.args = dict(keep=keep, drop_p=drop_p, rng_seed=rng_seed, rng_counter=rng_counter)
+        out, lse = ctx.fwd_bwd[0](q, k, v, n_heads, **ctx.args)
+        ctx.save_for_backward(q, k, v, lse)
+        ctx.n_heads = n_heads
+        return out
+
+    @staticmethod
+    def backward(ctx, go):
+        q, k, v, lse = ctx.saved_tensors
+        gq, gk, gv = ctx.fwd_bwd[1](q, k, v, lse, go, ctx.n_heads, **ctx.args)
+        return None, gq, gk, gv, None, None, None, None, None
+
+
+class SeqAttnFn:
     """seq_attn_fwd / seq_attn_bwd as one differentiable op of (q, k, v)."""
-
-    @staticmethod
-    def forward(ctx, q, k, v, n_heads, keep, drop_p, rng_seed, rng_counter):
-        q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
-        out, lse = seq_attn_fwd(q, k, v, n_heads, keep=keep, drop_p=drop_p, rng_seed=rng_seed, rng_counter=rng_counter)
-        ctx.save_for_backward(q, k, v, lse)
-        ctx.args = (n_heads, keep, drop_p, rng_seed, rng_counter)
-        return out
-
-    @staticmethod
-    def backward(ctx, go):
-        q, k, v, lse = ctx.saved_tensors
-        n_heads, keep, drop_p, rng_seed, rng_counter = ctx.args
-        gq, gk, gv = seq_attn_bwd(q, k, v, lse, go, n_heads, keep=keep, drop_p=drop_p, rng_seed=rng_seed,
-                                  rng_counter=rng_counter)
-        return gq, gk, gv, None, None, None, None, None
+    apply = staticmethod(functools.partial(_SeqAttn.apply, True))
 
 
-class SeqAttnFullFn(torch.autograd.Function):
+class SeqAttnFullFn:
     """seq_attn_full_fwd / seq_attn_full_bwd as one differentiable op of (q, k, v)."""
-
-    @staticmethod
-    def forward(ctx, q, k, v, n_heads, keep, drop_p, rng_seed, rng_counter):
-        q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
-        out, lse = seq_attn_full_fwd(q, k, v, n_heads, keep=keep, drop_p=drop_p, rng_seed=rng_seed,
-                                     rng_counter=rng_counter)
-        ctx.save_for_backward(q, k, v, lse)
-        ctx.args = (n_heads, keep, drop_p, rng_seed, rng_counter)
-        return out
-
-    @staticmethod
-    def backward(ctx, go):
-        q, k, v, lse = ctx.saved_tensors
-        n_heads, keep, drop_p, rng_seed, rng_counter = ctx.args
-        gq, gk, gv = seq_attn_full_bwd(q, k, v, lse, go, n_heads, keep=keep, drop_p=drop_p, rng_seed=rng_seed,
-                                       rng_counter=rng_counter)
-        return gq, gk, gv, None, None, None, None, None
+    apply = staticmethod(functools.partial(_SeqAttn.apply, False))
 
 
 def seq_bce_fwd_bwd(hidden, table, pos, neg, valid, n_valid=None, ws=None):
@@ -1593,10 +1584,12 @@ class SeqBceFn(torch.autograd.Function):
         ctx.plan, ctx.table_shape = plan, tuple(table.shape)
         return (loss2[0].to(torch.float32) + loss2[1].to(torch.float32))
 
-    @staticmethod
-    def backward(ctx, gout):
+    table_grad = staticmethod(rows_segment_sum)
+
+    @classmethod
+    def backward(cls, ctx, gout):
         gh, grows = ctx.saved_tensors
-        gt = rows_segment_sum(grows, ctx.plan, torch.zeros(ctx.table_shape, dtype=torch.float32, device=gh.device))
+        gt = cls.table_grad(grows, ctx.plan, torch.zeros(ctx.table_shape, dtype=torch.float32, device=gh.device))
         return gh * gout, gt * gout, None, None, None, None, None
 
 
@@ -1789,23 +1782,13 @@ class SeqEmbedFn(torch.autograd.Function):
         return gi, gp, None, None, None, None, None, None, None, None
 
 
-class SeqBceLiveFn(torch.autograd.Function):
+class SeqBceLiveFn(SeqBceFn):
     """SeqBceFn with the item table's gradient summed over the valid rows of [pos; neg] only (``plan`` = live_plan of
     [pos; neg] with live = [valid; valid]): the rows the kernel zeroed are never walked."""
 
     @staticmethod
-    def forward(ctx, hidden, table, pos, neg, valid, n_valid, plan):
-        loss2, gh, grows = seq_bce_fwd_bwd(hidden.contiguous(), table, pos, neg, valid, n_valid)
-        ctx.save_for_backward(gh, grows)
-        ctx.plan, ctx.table_shape = plan, tuple(table.shape)
-        return (loss2[0].to(torch.float32) + loss2[1].to(torch.float32))
-
-    @staticmethod
-    def backward(ctx, gout):
-        gh, grows = ctx.saved_tensors
-        gt = torch.zeros(ctx.table_shape, dtype=torch.float32, device=gh.device)
-        rows_live_sum([dict(x=grows, plan=ctx.plan, out=gt)])
-        return gh * gout, gt * gout, None, None, None, None, None
+    def table_grad(grows, plan, gt):
+        return rows_live_sum([dict(x=grows, plan=plan, out=gt)])[0]
 
 
 class InfoNceFn(torch.autograd.Function):
