@@ -788,6 +788,7 @@ srh_status_t srh_kmeans_update_f32(const float* d_x, int64_t n, const int32_t* d
  *   entries ASCENDING).  For query row q (d_query_rows[i], or row i when NULL) and every other row v sharing n > 0
  *   features with it:
  *       sim = (n / (n + s)) * (n / (norm[q] * norm[v] + 1e-8))     (s = shrinkage, each operation a rounded f64 one)
+ *   for any 0 <= s < 2^31: n + s is taken in f64, where it is exact, never in a 32-bit integer.
  *   d_norm[v] = sqrt((double)|A_v|) (np.sqrt of the degree, computed by the caller).  The best k by (sim desc,
  *   d_name_rank desc) -- heapq.nlargest(k, [(sim, name), ...]) when d_name_rank[v] is the rank of v's name in
  *   sorted(names).  Outputs (n_query x k, best first): d_out_ids (-1 padded), d_out_sims (0.0 padded), d_out_len.

@@ -40,8 +40,9 @@ constexpr int kScThreads = 256;
 constexpr int kScCap = 2048;
 constexpr double kMasked = -10e8;      // base/graph_recommender.py:50
 
+// n + s is formed in f64 (exact: both are below 2^31), so that a shrinkage near INT_MAX cannot wrap the sum as int would
 __device__ __forceinline__ double knn_sim(int n, int s, double norm_a, double norm_b) {
-  const double shrink = (double)n / (double)(n + s);
+  const double shrink = (double)n / ((double)n + (double)s);
   const double raw = (double)n / (norm_a * norm_b + 1e-8);
   return shrink * raw;
 }
@@ -174,8 +175,7 @@ __global__ __launch_bounds__(kNbThreads) void knn_neighbours_kernel(
       for (int t = tid; t < len0; t += kNbThreads) { b_sim[t] = r_sim[t]; b_rank[t] = r_rank[t]; b_id[t] = r_id[t]; }
       if (tid == 0) { s_last_sim = INFINITY; s_last_rank = INT_MAX; }
       __syncthreads();
-      int got = 0;
-      for (; got < k; ++got) {
+      for (int got = 0; got < k; ++got) {
         const double ls = s_last_sim;
         const int lr = s_last_rank;
         double ps = -1.0;
@@ -203,14 +203,14 @@ __global__ __launch_bounds__(kNbThreads) void knn_neighbours_kernel(
         if (tid == 0) {
           for (int w = 1; w < kNbWaves; ++w)
             if (nb_before(w_sim[w], w_rank[w], ps, pr)) { ps = w_sim[w]; pr = w_rank[w]; pid = w_id[w]; }
-          if (pid >= 0) { r_sim[got] = ps; r_rank[got] = pr; r_id[got] = pid; }
+          r_sim[got] = ps; r_rank[got] = pr; r_id[got] = pid;
           s_last_sim = ps;
           s_last_rank = pr;
         }
         __syncthreads();
-        if (s_last_rank < 0) break;                 // nothing left after the previous pick
       }
-      if (tid == 0) s_len = got;
+      // every round found a key: this branch runs with more than kNbCap distinct keys at hand and k <= kKnnMaxK < kNbCap
+      if (tid == 0) s_len = k;
       __syncthreads();
     }
   }

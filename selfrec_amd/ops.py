@@ -1195,6 +1195,8 @@ def knn_neighbours(a_indptr, a_indices, t_indptr, t_indices, norm, name_rank, k,
         raise SelfrecHipError(f"knn_neighbours: topK = {k} -- the kernels keep at most {KNN_MAX_K} neighbours per row")
     if shrinkage < 0:
         raise SelfrecHipError(f"knn_neighbours: negative shrinkage {shrinkage}")
+    if shrinkage >= 2 ** 31:
+        raise SelfrecHipError(f"knn_neighbours: shrinkage {shrinkage} -- the entry point takes a 32-bit value, below 2**31")
     n_rows = int(a_indptr.numel()) - 1
     if n_rows < 1 or int(norm.numel()) != n_rows or int(name_rank.numel()) != n_rows:
         raise SelfrecHipError("knn_neighbours: a_indptr, norm and name_rank must describe the same rows")

@@ -109,6 +109,18 @@ def test_topk_over_the_lds_limit_is_refused():
     assert rc == -1 and b"128" in lib.srh_last_error_string()
 
 
+def test_shrinkage_outside_32_bits_is_refused():
+    """the C entry point takes int32: 2**32 + 5 would arrive as 5"""
+    import torch
+    from selfrec_amd import ops
+    z = torch.zeros(3, dtype=torch.int32)
+    for s in (2 ** 31, 2 ** 32 + 5):
+        with pytest.raises(ops.SelfrecHipError, match=r"shrinkage.*2\*\*31"):
+            ops.knn_neighbours(z, z, z, z, z.double(), z, 50, s)
+    with pytest.raises(ops.SelfrecHipError, match="negative shrinkage"):
+        ops.knn_neighbours(z, z, z, z, z.double(), z, 50, -1)
+
+
 def test_host_heap_walk_f64_matches_heapq():
     from selfrec_amd import ops
     rng = np.random.default_rng(3)
