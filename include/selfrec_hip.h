@@ -536,7 +536,12 @@ srh_status_t srh_score_mask_topk(const float* d_user_emb, const int32_t* d_user_
  * Shape constants measured on the Yelp2018 shape (profiles/r03_m_*): chunk_rows 16384 (larger chunks fill the chip: 4096 ->
  * 16384 users per chunk is +20 %), sample_items 3072 in norm order (2048 .. 4096 are within 3 % of each other on trained
  * tables; round 3, catalogue order: 4096), cap 1024.  In the split path, pass 1 derives t~_u as the K-th largest of 256 disjoint group maxima of
- * the masked sample scores (a lower bound of their K-th largest: K distinct items attain it). */
+ * the masked sample scores (a lower bound of their K-th largest: K distinct items attain it).
+ * The workspace, with A(x) = ceil(x / 256) * 256, rows = chunk_rows, padded = ceil(n_items / 32) * 32:
+ *   every d:       A(4 rows sample_items) + 2 A(4 rows k) + 2 A(4 rows cap)      (bound slab, its ranked ids / scores, the survivor lists)
+ *   d = 64 / 128:  + A(2 padded d) + A(2 rows d) + A(4 rows) + 6 A(4 padded) + A(the radix sort's scratch for n_items pairs)
+ *                  (bf16 item image, bf16 query rows and their norms, item norms and the norm order, the sort library's own scratch)
+ * srh_score_mask_topk_filtered_ws_bytes returns 0 if an argument is not positive; it needs no device. */
 int64_t srh_score_mask_topk_filtered_ws_bytes(int64_t chunk_rows, int64_t sample_items, int32_t k, int32_t cap,
                                               int64_t n_items, int32_t d);
 srh_status_t srh_score_mask_topk_filtered(const float* d_user_emb, const int32_t* d_user_ids, int64_t n_query,

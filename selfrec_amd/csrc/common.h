@@ -164,6 +164,20 @@ __device__ __forceinline__ float wave_sum_f(float v) {
 }
 __device__ __forceinline__ float sgnf(float x) { return (x > 0.f) ? 1.f : ((x < 0.f) ? -1.f : 0.f); }
 
+// first position in the ascending a[lo, hi) whose value is >= x (hi if there is none); a: global memory or LDS
+__device__ __forceinline__ int lower_bound_i32(const int32_t* a, int lo, int hi, int x) {
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (a[mid] < x) lo = mid + 1; else hi = mid;
+  }
+  return lo;
+}
+// is x one of the ascending a[lo, hi)?  (a CSR row with sorted columns; an empty range reads nothing)
+__device__ __forceinline__ bool sorted_contains(const int32_t* a, int lo, int hi, int x) {
+  const int p = lower_bound_i32(a, lo, hi, x);
+  return p < hi && a[p] == x;
+}
+
 // Counter-based noise: every element's uniform is a pure function of (seed, counter, element),
 // so there is no generator state in memory and a captured graph replays with fresh noise by
 // bumping one device-side counter.  The mixer is the 2-multiply "lowbias32" integer hash (full

@@ -15,6 +15,19 @@ using namespace srh;
 
 typedef float floatx16 __attribute__((ext_vector_type(16)));
 
+// ranking order: score descending, then id ascending
+__device__ __forceinline__ bool before(float sa, int ia, float sb, int ib) {
+  return (sa > sb) || (sa == sb && ia < ib);
+}
+// the user behind query row `row` of a chunk that starts at user_base: the row of the mask CSR
+__device__ __forceinline__ int query_user(const int32_t* user_ids, int user_base, int row) {
+  return user_ids ? user_ids[row] : user_base + row;
+}
+// wave compaction: the number of set ballot bits below this lane = its slot among the lanes that voted
+__device__ __forceinline__ int lane_rank(unsigned long long bal) {
+  return __builtin_amdgcn_mbcnt_hi((unsigned)(bal >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bal, 0));
+}
+
 // C[m0+i][n0+j] for a 32x32 tile per wave; each wave keeps its 32 A rows in registers and
 // walks TILES_PER_WAVE column tiles.  Operand layout of v_mfma_f32_32x32x2_f32: lane l gives
 // A[i=l&31][k=l>>5] and B[k=l>>5][j=l&31]; the k index is a free summation index, so lane
@@ -149,7 +162,7 @@ __global__ __launch_bounds__(256) void mask_kernel(const int32_t* __restrict__ u
   const int q = (int)((blockIdx.x * 256u + threadIdx.x) >> 6);
   if (q >= m) return;
   const int lane = threadIdx.x & 63;
-  const int u = user_ids ? user_ids[q] : user_base + q;
+  const int u = query_user(user_ids, user_base, q);
   const int s = indptr[u], e = indptr[u + 1];
   for (int p = s + lane; p < e; p += 64) {
     const int item = indices[p];
@@ -175,16 +188,11 @@ __global__ __launch_bounds__(256) void cand_topk_kernel(const int32_t* __restric
   if (threadIdx.x == 0) s_n = 0;
   __syncthreads();
   // training items of the user are dropped here (graph_recommender.py:49-50 masks them to -10e8)
-  const int u = user_ids ? user_ids[row] : user_base + row;
+  const int u = query_user(user_ids, user_base, row);
   const int rs = r_indptr ? r_indptr[u] : 0, re = r_indptr ? r_indptr[u + 1] : 0;
   for (int t = threadIdx.x; t < c; t += 256) {
     const int id = cand_id[(size_t)row * cap + t];
-    int lo = rs, hi = re;
-    while (lo < hi) {
-      const int mid = (lo + hi) >> 1;
-      if (r_indices[mid] < id) lo = mid + 1; else hi = mid;
-    }
-    if (lo < re && r_indices[lo] == id) continue;
+    if (sorted_contains(r_indices, rs, re, id)) continue;
     const int at = atomicAdd(&s_n, 1);
     s_val[at] = cand_sc[(size_t)row * cap + t];
     s_idx[at] = id;
@@ -195,7 +203,7 @@ __global__ __launch_bounds__(256) void cand_topk_kernel(const int32_t* __restric
     const float v = s_val[t];
     const int id = s_idx[t];
     int rank = 0;
-    for (int j = 0; j < nv; ++j) rank += (s_val[j] > v) || (s_val[j] == v && s_idx[j] < id);
+    for (int j = 0; j < nv; ++j) rank += before(s_val[j], s_idx[j], v, id);
     if (rank < k) {
       out_ids[(size_t)row * k + rank] = id;
       out_scores[(size_t)row * k + rank] = v;
@@ -205,45 +213,29 @@ __global__ __launch_bounds__(256) void cand_topk_kernel(const int32_t* __restric
 
 
 // ---------------------------------------------------------------------------------------
-// The FILTER pass on the bf16 pipe (round 3; margins per item and one-term products: round 4).  The filter only has to
-// decide "can this score reach the row's bound?" -- it never has to report a score -- so it runs on bf16 operands against
-// rigorous error bounds; the few dozen survivors per user are then RE-SCORED with the very instruction sequence of
-// gemm_nt_kernel (so ids and scores stay bit-identical to the plain pipeline) and ranked.
-//   s~_uj = the bf16 product the MFMAs form,  |s~_uj - s_uj| <= delta_uj = c |u| |i_j|,   c = kFilterMargin:
-//   SRH_F16_TERMS  products per 16 dimensions                 c
-//   3              u_hi.i_hi + u_hi.i_lo + u_lo.i_hi           5e-5     (dropped lo.lo: 3 * 2^-18)
-//   2              u_hi.i_hi + u_lo.i_hi                       1.99e-3  (the item side rounded to bf16: 2^-9 + 2^-18)
-//   1 (default)    u_hi.i_hi                                   3.94e-3  (both sides rounded: 2^-8 + 2^-18)
-//   -- |fl_bf16(x) - x| <= 2^-9 |x| (round to nearest even, 8 significant bits), the products are exact in f32, Cauchy-Schwarz
-//   over the d terms, and the f32 accumulation of d + 1 <= 129 addends (the accumulator starts at -T, see below) adds at most
-//   2 (d + 1) 2^-24 |u||i_j| = 1.6e-5 |u||i_j| wherever it matters (|T| <= |u||i_j| for any item that can reach T).
-// The margin is PER ITEM: with one bound for the whole catalogue (round 3: c |u| max_j |i_j|) a few popular items of large
-// norm -- trained tables have them: 100x the typical norm after 1300 steps -- widen everybody's margin, harmless at
-// c = 4e-5 and ruinous at 4e-3 (984 of 31.5 k users overflowed their candidate lists).  Per item the margin scales with the
-// score it guards.  The margin only decides how many items reach the exact re-score: near a row's K-th best score the
-// catalogue is thin, so a 100x wider one adds a handful of survivors per user (50 -> 60) while the MFMA work and the item
-// image staged through LDS drop to a third / a half.
+// The FILTER pass on the bf16 pipe.  The filter only has to decide "can this score reach the row's bound?" -- it never has
+// to report a score -- so it runs on bf16 operands against rigorous error bounds; the few dozen survivors per user are then
+// RE-SCORED with the very instruction sequence of gemm_nt_kernel (so ids and scores stay bit-identical to the plain
+// pipeline) and ranked.
+//   s~_uj = u_hi . i_hi, the product the MFMAs form from both operands rounded to bf16:
+//   |s~_uj - s_uj| <= delta_uj = c |u| |i_j|,  c = kFilterMargin = 3.94e-3 >= 2^-8 + 2^-18 + 1.6e-5
+//   -- |fl_bf16(x) - x| <= 2^-9 |x| (round to nearest even, 8 significant bits) on either side, the products are exact in f32,
+//   Cauchy-Schwarz over the d terms, and the f32 accumulation of d + 1 <= 129 addends (the accumulator starts at -T, see
+//   below) adds at most 2 (d + 1) 2^-24 |u||i_j| = 1.6e-5 |u||i_j| wherever it matters (|T| <= |u||i_j| for any item that can
+//   reach T).
+// The margin is PER ITEM: trained tables have a few popular items of 100x the typical norm, and one bound for the whole
+// catalogue would let them widen everybody's margin; per item the margin scales with the score it guards.  The margin only
+// decides how many items reach the exact re-score: near a row's K-th best score the catalogue is thin.
 //   bound stage:  slab[u][j] = s~_uj - delta_uj <= s_uj for a leading slice of the catalogue; T_u = a lower bound of its
 //                 K-th largest entry (training items masked) <= the exact K-th best score of the row;
 //   filter:       a top-K item has s_uj >= T_u, hence s~_uj + delta_uj >= T_u: the accumulator starts at -T_u and the test
 //                 is fma(c |u|, |i_j|, acc) >= 0 -- one FMA per output and ONE comparison per 32 x 32 block (the maximum);
 //   re-score:     L_j = s~ - delta, U_j = s~ + delta; tau = the K-th largest L_j of the unmasked survivors <= the exact K-th
 //                 best; only survivors with U_j >= tau can be in the exact top-K: those are re-scored exactly and ranked.
-// Where a ranking's 1.05 ms go (31.5 k users, trained tables, tools/gpu_session.sh evalbreakab with -DSRH_F16_EXP=1 / 2 builds):
-// MFMAs + operand staging of the filter 0.17, its epilogue 0.25 (four blocks in five hold a survivor: 1.6 per 32 x 32 block),
-// writing the survivors out 0.10, the re-score 0.19, the bound stage (slab, mask, bound) 0.21, the rest 0.13.  Tried on top
-// and dropped, all within +-0.07 ms of this form: survivor lists private to (row, item range) with LDS slot counters instead
-// of device-scope atomics (the atomics are not what the flush costs), long staging lists flushed when half full (seven
-// waves wait at the stage barrier for the one that flushes), four returning atomics in flight per lane, wave-uniform
-// ballots per row quad and output instead of the bit mask + select loop.
+// (How this form was arrived at, and what was measured and dropped on the way: DESIGN.md 4.4.)
 // ---------------------------------------------------------------------------------------
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-#ifndef SRH_F16_TERMS
-#define SRH_F16_TERMS 1
-#endif
-constexpr int kF16Terms = SRH_F16_TERMS;
-static_assert(kF16Terms >= 1 && kF16Terms <= 3, "SRH_F16_TERMS: 1, 2 or 3");
-constexpr float kFilterMargin = kF16Terms == 3 ? 5e-5f : (kF16Terms == 2 ? 1.99e-3f : 3.94e-3f);
+constexpr float kFilterMargin = 3.94e-3f;
 // the survivor's score is handed on as acc + T (the accumulator held s~ - T): one more rounding of size 2^-24 (|T| + |s~|)
 constexpr float kFilterAbsSlack = 3e-7f;
 
@@ -278,16 +270,14 @@ static size_t filt_sort_temp_bytes(int64_t n) {
   return bytes;
 }
 
-// rows of an f32 table as bf16 hi / lo images + the row's L2 norm; the table's largest norm in *max_norm (float bits
-// compare like unsigned ints for non-negative floats).  FRAG = false: row-major images (the query rows: each wave loads
-// its A operands once).  FRAG = true: FRAGMENT-LINEAR images of the item table -- per 32-row tile, per image, per MFMA
-// step s one contiguous 1 KB fragment whose lane l = 32 h + r holds row 32 tile + r, dimensions [16 s + 8 h, + 8): exactly
-// what lane l feeds v_mfma_f32_32x32x16_bf16 as its B operand, so a workgroup copies whole tiles into LDS with direct
+// rows of an f32 table rounded to bf16 + the row's L2 norm.  FRAG = false: a row-major image (the query rows: each wave
+// loads its A operands once).  FRAG = true: the FRAGMENT-LINEAR image of the item table -- per 32-row tile, per MFMA step s
+// one contiguous 1 KB fragment whose lane l = 32 h + r holds row 32 tile + r, dimensions [16 s + 8 h, + 8): exactly what
+// lane l feeds v_mfma_f32_32x32x16_bf16 as its B operand, so a workgroup copies whole tiles into LDS with direct
 // global -> LDS loads and every wave reads its operand with one conflict-free ds_read_b128.
 template <int LPR, bool FRAG>
 __global__ __launch_bounds__(256) void split_rows_kernel(const float* __restrict__ X, const int32_t* __restrict__ rows, int n,
-                                                         uint16_t* __restrict__ hi, uint16_t* __restrict__ lo,
-                                                         float* __restrict__ norm, unsigned int* __restrict__ max_norm) {
+                                                         uint16_t* __restrict__ img, float* __restrict__ norm) {
   constexpr int G = 64 / LPR, D = 4 * LPR, KS = D / 16;
   const int lane = threadIdx.x & 63, g = lane / LPR, sub = lane % LPR;
   const int r = (int)((blockIdx.x * 256u + threadIdx.x) >> 6) * G + g;
@@ -295,43 +285,19 @@ __global__ __launch_bounds__(256) void split_rows_kernel(const float* __restrict
   const int src = valid ? (rows ? rows[r] : r) : 0;
   const float4 v = reinterpret_cast<const float4*>(X)[(size_t)src * LPR + sub];
   const float ss = group_sum<LPR>(f4_dot(v, v));
-  if (max_norm) {
-    // one atomic per workgroup: same-address atomics serialise at ~11 ns each on this chip (one per row: 111 us for
-    // 38 k items)
-    __shared__ float s_mx[4];
-    float mx = valid ? sqrtf(ss) : 0.f;
-    for (int msk = 1; msk < 64; msk <<= 1) mx = fmaxf(mx, __shfl_xor(mx, msk));
-    if (lane == 0) s_mx[threadIdx.x >> 6] = mx;
-    __syncthreads();
-    if (threadIdx.x == 0) atomicMax(max_norm, __float_as_uint(fmaxf(fmaxf(s_mx[0], s_mx[1]), fmaxf(s_mx[2], s_mx[3]))));
-  }
   if (!valid) return;
   const float f[4] = {v.x, v.y, v.z, v.w};
-  uint16_t h[4], l[4];
+  uint16_t h[4];
 #pragma unroll
-  for (int t = 0; t < 4; ++t) {
-    const __bf16 bh = (__bf16)f[t];
-    h[t] = __builtin_bit_cast(uint16_t, bh);
-    l[t] = __builtin_bit_cast(uint16_t, (__bf16)(f[t] - (float)bh));
-  }
+  for (int t = 0; t < 4; ++t) h[t] = __builtin_bit_cast(uint16_t, (__bf16)f[t]);
   const uint2 ph = make_uint2(h[0] | ((uint32_t)h[1] << 16), h[2] | ((uint32_t)h[3] << 16));
-  const uint2 pl = make_uint2(l[0] | ((uint32_t)l[1] << 16), l[2] | ((uint32_t)l[3] << 16));
+  size_t at = ((size_t)r * LPR + sub) * 4;
   if (FRAG) {
     const int col0 = 4 * sub, st = col0 >> 4, hh = (col0 >> 3) & 1, e0 = col0 & 7;
-    const size_t tile = (size_t)(r >> 5);
-    const size_t at_hi = ((tile * 2 + 0) * KS + st) * 512 + (size_t)(hh * 32 + (r & 31)) * 8 + e0;
-    const size_t at_lo = ((tile * 2 + 1) * KS + st) * 512 + (size_t)(hh * 32 + (r & 31)) * 8 + e0;
-    *reinterpret_cast<uint2*>(hi + at_hi) = ph;            // (hi: the base of the interleaved image; lo unused)
-    *reinterpret_cast<uint2*>(hi + at_lo) = pl;
-  } else {
-    const size_t at = ((size_t)r * LPR + sub) * 4;
-    *reinterpret_cast<uint2*>(hi + at) = ph;
-    *reinterpret_cast<uint2*>(lo + at) = pl;
+    at = ((size_t)(r >> 5) * KS + st) * 512 + (size_t)(hh * 32 + (r & 31)) * 8 + e0;
   }
-  if (sub == 0) {
-    const float nr = sqrtf(ss);
-    if (norm) norm[r] = nr;
-  }
+  *reinterpret_cast<uint2*>(img + at) = ph;
+  if (sub == 0) norm[r] = sqrtf(ss);
 }
 
 struct Filter16Args {
@@ -342,7 +308,7 @@ struct Filter16Args {
   const int32_t* order;        // image row -> item id (the image holds the items by norm, largest first)
   int32_t* cnt;
   int32_t* cand_id;
-  float* cand_sc;              // the split-bf16 score of the candidate (within delta_u of the exact one)
+  float* cand_sc;              // the bf16 score of the candidate (within delta_uj of the exact one)
   int cap;
 };
 
@@ -350,48 +316,36 @@ __device__ __forceinline__ void glds16_b(const void* gsrc, void* ldst) {
   __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gsrc,
                                    (__attribute__((address_space(3))) void*)ldst, 16, 0, 0);
 }
-#ifndef SRH_F16_EXP
-#define SRH_F16_EXP 0
-#endif
-constexpr int kF16StageCap = 256;   // survivors a wave collects in LDS between two flushes (one per stage of item tiles)
+constexpr int kF16Waves = 8;         // one 32-row MFMA block per wave: 256 query rows per workgroup
+constexpr int kF16StageCap = 128;    // survivors a wave collects in LDS between two flushes (one per stage of item tiles)
 constexpr int kF16NormBytes = 1024;  // the staged tiles' item norms: <= 8 tiles x 32 floats per stage
-constexpr int kF16Lds = 2 * (32768 + kF16NormBytes) + 4 * kF16StageCap * (4 + 4 + 2);   // two stages (+ norms) + the survivor lists
-#ifndef SRH_F16_UB
-#define SRH_F16_UB 1                // 32-row MFMA blocks per wave: 1 (8 waves per 256-row workgroup) or 2 (4 waves; the first version)
-#endif
+constexpr int kF16Lds = 2 * (32768 + kF16NormBytes) + kF16Waves * kF16StageCap * (4 + 4 + 2);   // two stages (+ norms) + the survivor lists
 
-// One workgroup: 256 query rows (UB = 1: eight waves x one 32-row MFMA block, 110 VGPRs, four waves per SIMD with two workgroups
-// per CU -- 400 -> 303 us per 16384-row chunk against UB = 2, the first version: four waves x two blocks, 189 VGPRs, two waves per
-// SIMD, where one wave's operand reads / epilogue and the other's MFMAs overlapped little; operands resident in registers) against a
-// contiguous range of 32-item tiles, which it copies into LDS a stage of ST tiles at a time (double-buffered: the copy
-// of stage k + 1 runs under the MFMAs of stage k) -- one L2 read of the item images per 256 query rows instead of one
-// per 64, and no wave ever waits for a global round trip per tile (the first version, every wave streaming its own B
-// tiles from L2 with one tile of prefetch, ran at 217 us per 4096 x 38048 chunk for 24 us of MFMA work).
+// One workgroup: 256 query rows (eight waves x one 32-row MFMA block, operands resident in registers; four waves per SIMD
+// with two workgroups per CU) against a contiguous range of 32-item tiles, which it copies into LDS a stage of ST tiles at
+// a time (double-buffered: the copy of stage k + 1 runs under the MFMAs of stage k) -- one L2 read of the item image per
+// 256 query rows, and no wave ever waits for a global round trip per tile.
 // Operand layout of v_mfma_f32_32x32x16_bf16: lane l gives A[i = l & 31][k = 8 (l >> 5) .. +7], B[k ..][j = l & 31]; k is a
 // free summation index: MFMA step s takes dimensions [16 s + 8 h, + 8) from lane half h.
-// SLAB: instead of filtering, write the split-bf16 scores of the item range into a (m x n) slab -- the bound stage (the
-// K-th score over a leading slice of the catalogue), which then costs a quarter of the f32 GEMM it replaces; the bound
-// derived from approximate scores is lowered by one more delta_u (see srh_score_mask_topk_filtered).
-template <int D, bool SLAB = false, int UB = 2>
-__global__ __launch_bounds__(512 / UB) void filter16_kernel(const uint16_t* __restrict__ Uhi, const uint16_t* __restrict__ Ulo,
-                                                       const uint16_t* __restrict__ Ifrag, int m, int n,
-                                                       Filter16Args f, float* __restrict__ C = nullptr) {
-  constexpr int KS = D / 16;
-  constexpr int TILE_BYTES = 2 * KS * 1024;          // hi fragments then lo fragments of one 32-item tile (the global image)
-  constexpr int FR = kF16Terms == 3 ? 2 * KS : KS;   // fragments of a tile this build stages: hi + lo, or hi only
-  // tiles per stage: 8 (d = 64 hi-only; 4 with the lo fragments), 4 (d = 128; 2).  The slab launch -- a slice of ~100 tiles dealt
-  // round-robin over 8 workgroups per row block -- takes half-size stages so that the deal comes out even.
-  constexpr int ST = (SLAB ? 16384 : 32768) / (FR * 1024);
+// SLAB: instead of filtering, write the bf16 scores of the item range, each lowered by its own margin, into a (m x n) slab
+// -- the bound stage (the K-th score over a leading slice of the catalogue), which then costs a quarter of the f32 GEMM it
+// replaces.
+template <int D, bool SLAB = false>
+__global__ __launch_bounds__(64 * kF16Waves) void filter16_kernel(const uint16_t* __restrict__ Uimg, const uint16_t* __restrict__ Ifrag,
+                                                                  int m, int n, Filter16Args f, float* __restrict__ C = nullptr) {
+  constexpr int KS = D / 16;                         // MFMA steps = 1 KB fragments per 32-item tile
+  // tiles per stage: 8 (d = 64), 4 (d = 128).  The slab launch -- a slice of ~100 tiles dealt round-robin over 8 workgroups
+  // per row block -- takes half-size stages so that the deal comes out even.
+  constexpr int ST = (SLAB ? 16384 : 32768) / (KS * 1024);
   extern __shared__ __attribute__((aligned(16))) unsigned char f16_smem[];
-  constexpr int STAGE_BYTES = ST * FR * 1024 + kF16NormBytes;      // 32 KB of fragments, then the tiles' item norms
+  constexpr int STAGE_BYTES = ST * KS * 1024 + kF16NormBytes;      // up to 32 KB of fragments, then the tiles' item norms
   static_assert(ST * 128 <= kF16NormBytes, "norm slot of a stage");
-  constexpr int WAVES = 8 / UB, CAP = kF16StageCap * UB / 2;       // (same LDS either way: 8 shorter lists or 4 longer ones)
   int* s_col = reinterpret_cast<int*>(f16_smem + 2 * STAGE_BYTES);
-  float* s_sc = reinterpret_cast<float*>(s_col + WAVES * CAP);
-  short* s_row = reinterpret_cast<short*>(s_sc + WAVES * CAP);
+  float* s_sc = reinterpret_cast<float*>(s_col + kF16Waves * kF16StageCap);
+  short* s_row = reinterpret_cast<short*>(s_sc + kF16Waves * kF16StageCap);
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int r32 = lane & 31, h = lane >> 5;
-  const int m0 = blockIdx.y * 256 + wv * 32 * UB;
+  const int m0 = blockIdx.y * 256 + wv * 32;
   const int n_tiles = (n + 31) / 32;
   // The item image is in NORM order (largest first), and that is where a row's survivors are: the workgroups of one row block
   // take the STAGES of item tiles round-robin -- x, x + X, x + 2 X, ... -- so that each of them sees large and small norms
@@ -401,36 +355,26 @@ __global__ __launch_bounds__(512 / UB) void filter16_kernel(const uint16_t* __re
   const int t_begin = blockIdx.x * ST, t_step = gridDim.x * ST;
   if (t_begin >= t_end) return;
   const bool live = m0 < m;                          // (a wave beyond the chunk's rows still copies and synchronises)
-  auto ld8 = [](const uint16_t* p) { return __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(p)); };
-  bf16x8 ah[UB][KS], al[UB][KS];
-  float thr[UB][16];             // T_row of the rows this lane holds results for (+inf beyond the chunk: nothing passes)
-  float cu[UB][16];              // c |u_row|: times the item's norm = the margin of one score
+  bf16x8 a[KS];
+  float thr[16];                 // T_row of the rows this lane holds results for (+inf beyond the chunk: nothing passes)
+  float cu[16];                  // c |u_row|: times the item's norm = the margin of one score
   {
+    const int ar = min(m0 + r32, m - 1);
 #pragma unroll
-    for (int ub = 0; ub < UB; ++ub) {
-      const int ar = min(m0 + 32 * ub + r32, m - 1);
+    for (int s = 0; s < KS; ++s)
+      a[s] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(Uimg + (size_t)ar * D + 16 * s + 8 * h));
 #pragma unroll
-      for (int s = 0; s < KS; ++s) {
-        ah[ub][s] = ld8(Uhi + (size_t)ar * D + 16 * s + 8 * h);
-        if (kF16Terms >= 2) al[ub][s] = ld8(Ulo + (size_t)ar * D + 16 * s + 8 * h);
-      }
-#pragma unroll
-      for (int t = 0; t < 16; ++t) {
-        const int row = m0 + 32 * ub + (t & 3) + 8 * (t >> 2) + 4 * h;
-        cu[ub][t] = (row < m) ? kFilterMargin * f.u_norm[row] : 0.f;
-        thr[ub][t] = SLAB ? 0.f : ((row < m) ? f.thr[(size_t)row * f.thr_stride] : INFINITY);
-      }
+    for (int t = 0; t < 16; ++t) {
+      const int row = m0 + (t & 3) + 8 * (t >> 2) + 4 * h;
+      cu[t] = (row < m) ? kFilterMargin * f.u_norm[row] : 0.f;
+      thr[t] = SLAB ? 0.f : ((row < m) ? f.thr[(size_t)row * f.thr_stride] : INFINITY);
     }
   }
-  int* stage_col = s_col + wv * CAP;
-  float* stage_sc = s_sc + wv * CAP;
-  short* stage_row = s_row + wv * CAP;
+  int* stage_col = s_col + wv * kF16StageCap;
+  float* stage_sc = s_sc + wv * kF16StageCap;
+  short* stage_row = s_row + wv * kF16StageCap;
   int staged = 0;                // wave-uniform
   auto flush = [&]() {
-#if SRH_F16_EXP == 1                          // (timing experiment: what the survivors' global atomics + stores cost)
-    staged = 0;
-    return;
-#endif
     for (int e = lane; e < staged; e += 64) {
       const int row = m0 + stage_row[e];
       const int slot = atomicAdd(f.cnt + row, 1);
@@ -443,16 +387,12 @@ __global__ __launch_bounds__(512 / UB) void filter16_kernel(const uint16_t* __re
   };
   const unsigned char* img = reinterpret_cast<const unsigned char*>(Ifrag);
   auto copy_stage = [&](int t0, unsigned char* dst) {           // tiles [t0, min(t0 + ST, t_end)) -> dst
-    const int frags = min(ST, t_end - t0) * FR;
-    const unsigned char* src = img + (size_t)t0 * TILE_BYTES;
-    for (int k = wv; k < frags; k += WAVES) {
-      // (hi-only builds skip the lo half of every tile of the global image)
-      const size_t from = (FR == 2 * KS) ? (size_t)k * 1024 : (size_t)(k / KS) * TILE_BYTES + (size_t)(k % KS) * 1024;
-      glds16_b(src + from + lane * 16, dst + k * 1024);
-    }
+    const int frags = min(ST, t_end - t0) * KS;
+    const unsigned char* src = img + (size_t)t0 * (KS * 1024);
+    for (int k = wv; k < frags; k += kF16Waves) glds16_b(src + (size_t)k * 1024 + lane * 16, dst + k * 1024);
     // the tiles' item norms (128 B per tile) behind the fragments: one 16-byte direct load per lane of one wave
-    if (wv == (frags % WAVES) && lane * 4 < min(ST, t_end - t0) * 32)
-      glds16_b(reinterpret_cast<const unsigned char*>(f.item_norm) + (size_t)t0 * 128 + lane * 16, dst + ST * FR * 1024);
+    if (wv == (frags % kF16Waves) && lane * 4 < min(ST, t_end - t0) * 32)
+      glds16_b(reinterpret_cast<const unsigned char*>(f.item_norm) + (size_t)t0 * 128 + lane * 16, dst + ST * KS * 1024);
   };
   copy_stage(t_begin, f16_smem);
   int cur = 0;
@@ -464,79 +404,59 @@ __global__ __launch_bounds__(512 / UB) void filter16_kernel(const uint16_t* __re
       const unsigned char* buf = f16_smem + cur * STAGE_BYTES;
       const int nt = min(ST, t_end - t0);
       for (int tt = 0; tt < nt; ++tt) {
-        bf16x8 bh[KS], bl[KS];
+        bf16x8 b[KS];
 #pragma unroll
-        for (int s = 0; s < KS; ++s) {
-          bh[s] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(buf + (tt * FR + s) * 1024 + lane * 16));
-          if (kF16Terms == 3) bl[s] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(buf + (tt * FR + KS + s) * 1024 + lane * 16));
-        }
+        for (int s = 0; s < KS; ++s)
+          b[s] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(buf + (tt * KS + s) * 1024 + lane * 16));
         const int col = (t0 + tt) * 32 + r32;
-        const float nj = *reinterpret_cast<const float*>(buf + ST * FR * 1024 + (tt * 32 + r32) * 4);     // |i_col|
+        const float nj = *reinterpret_cast<const float*>(buf + ST * KS * 1024 + (tt * 32 + r32) * 4);     // |i_col|
+        floatx16 acc;
 #pragma unroll
-        for (int ub = 0; ub < UB; ++ub) {
-          floatx16 acc;
+        for (int t = 0; t < 16; ++t) acc[t] = -thr[t];                     // (the slab stage: thr = 0)
 #pragma unroll
-          for (int t = 0; t < 16; ++t) acc[t] = -thr[ub][t];                 // (the slab stage: thr = 0)
+        for (int s = 0; s < KS; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[s], b[s], acc, 0, 0, 0);
+        if (SLAB) {
+          // a LOWER bound of every exact score of the slice: the bound stage ranks these
 #pragma unroll
-          for (int s = 0; s < KS; ++s) {
-            if (kF16Terms >= 2) acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[ub][s], bh[s], acc, 0, 0, 0);
-            if (kF16Terms == 3) acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[ub][s], bl[s], acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[ub][s], bh[s], acc, 0, 0, 0);
+          for (int t = 0; t < 16; ++t) {
+            const int row = m0 + (t & 3) + 8 * (t >> 2) + 4 * h;
+            if (row < m && col < n) C[(size_t)row * n + col] = __builtin_fmaf(-cu[t], nj, acc[t]);
           }
-          if (SLAB) {
-            // a LOWER bound of every exact score of the slice: the bound stage ranks these
+          continue;
+        }
+        // Nothing passes in one block of five: that case is straight-line code -- one FMA per output (the score's own
+        // margin added to s~ - T), their maximum by v_max3, ONE comparison and ONE ballot per 32 x 32 block.
+        float e[16];
 #pragma unroll
-            for (int t = 0; t < 16; ++t) {
-              const int row = m0 + 32 * ub + (t & 3) + 8 * (t >> 2) + 4 * h;
-              if (row < m && col < n) C[(size_t)row * n + col] = __builtin_fmaf(-cu[ub][t], nj, acc[t]);
-            }
-            continue;
+        for (int t = 0; t < 16; ++t) e[t] = __builtin_fmaf(cu[t], nj, acc[t]);
+        float mx = fmaxf(fmaxf(e[0], e[1]), e[2]);
+#pragma unroll
+        for (int t = 3; t < 15; t += 2) mx = fmaxf(fmaxf(mx, e[t]), e[t + 1]);
+        mx = fmaxf(mx, e[15]);
+        if (col >= n) mx = -1.f;
+        unsigned long long bal = __builtin_amdgcn_ballot_w64(mx >= 0.f);
+        if (bal == 0) continue;
+        unsigned pm = 0;
+#pragma unroll
+        for (int t = 0; t < 16; ++t) pm |= (e[t] >= 0.f ? 1u : 0u) << t;           // (rows >= m: -inf)
+        if (col >= n) pm = 0;
+        bal = __builtin_amdgcn_ballot_w64(pm != 0);
+        while (bal != 0) {                                                 // wave-uniform; one pass per survivor of the
+          const bool act = pm != 0;                                        // lane that has the most (almost always 1)
+          const int t = act ? __builtin_ctz(pm) : 0;
+          pm &= pm - 1u;
+          float sc = acc[0] + thr[0];
+#pragma unroll
+          for (int k = 1; k < 16; ++k) sc = (t == k) ? acc[k] + thr[k] : sc;       // (registers cannot be indexed by t)
+          if (act) {
+            const int at = staged + lane_rank(bal);
+            stage_row[at] = (short)((t & 3) + 8 * (t >> 2) + 4 * h);
+            stage_col[at] = col;
+            stage_sc[at] = sc;
           }
-#if SRH_F16_EXP == 2                          // (timing experiment: MFMAs + operand traffic + barriers alone)
-          {
-            float mx = acc[0];
-#pragma unroll
-            for (int t = 1; t < 16; ++t) mx = fmaxf(mx, acc[t]);
-            if (mx == 12345.678f) f.cand_sc[0] = mx;
-            continue;
-          }
-#endif
-          // Nothing passes in one block of five: that case is straight-line code -- one FMA per output (the score's own
-          // margin added to s~ - T), their maximum by v_max3, ONE comparison and ONE ballot per 32 x 32 block.  (Round 3 packed
-          // 16 comparisons into a bit mask first: two VALU operations per output; its first version tested a ballot per
-          // accumulator register: 32 taken branches per tile.)
-          float e[16];
-#pragma unroll
-          for (int t = 0; t < 16; ++t) e[t] = __builtin_fmaf(cu[ub][t], nj, acc[t]);
-          float mx = fmaxf(fmaxf(e[0], e[1]), e[2]);
-#pragma unroll
-          for (int t = 3; t < 15; t += 2) mx = fmaxf(fmaxf(mx, e[t]), e[t + 1]);
-          mx = fmaxf(mx, e[15]);
-          if (col >= n) mx = -1.f;
-          unsigned long long bal = __builtin_amdgcn_ballot_w64(mx >= 0.f);
-          if (bal == 0) continue;
-          unsigned pm = 0;
-#pragma unroll
-          for (int t = 0; t < 16; ++t) pm |= (e[t] >= 0.f ? 1u : 0u) << t;           // (rows >= m: -inf)
-          if (col >= n) pm = 0;
+          staged += __builtin_popcountll(bal);
+          if (staged > kF16StageCap - 64) flush();                                 // (rare: a tie-heavy block)
           bal = __builtin_amdgcn_ballot_w64(pm != 0);
-          while (bal != 0) {                                                 // wave-uniform; one pass per survivor of the
-            const bool act = pm != 0;                                        // lane that has the most (almost always 1)
-            const int t = act ? __builtin_ctz(pm) : 0;
-            pm &= pm - 1u;
-            float sc = acc[0] + thr[ub][0];
-#pragma unroll
-            for (int k = 1; k < 16; ++k) sc = (t == k) ? acc[k] + thr[ub][k] : sc;       // (registers cannot be indexed by t)
-            if (act) {
-              const int at = staged + __builtin_amdgcn_mbcnt_hi((unsigned)(bal >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bal, 0));
-              stage_row[at] = (short)(32 * ub + (t & 3) + 8 * (t >> 2) + 4 * h);
-              stage_col[at] = col;
-              stage_sc[at] = sc;
-            }
-            staged += __builtin_popcountll(bal);
-            if (staged > CAP - 64) flush();                                 // (rare: a tie-heavy block)
-            bal = __builtin_amdgcn_ballot_w64(pm != 0);
-          }
         }
       }
       if (staged > 0) flush();      // once per stage, right before the wait the pipeline makes anyway
@@ -549,11 +469,34 @@ __global__ __launch_bounds__(512 / UB) void filter16_kernel(const uint16_t* __re
 //   L_j = s~ - delta_j <= s_j <= U_j = s~ + delta_j;  tau = the K-th largest L_j of the unmasked survivors: K items have
 //   s >= tau, so the exact K-th best is >= tau and an exact top-K item has U_j >= tau -- the candidates of the second round
 //   (K ... a few dozen per user: their item rows are the only ones gathered again).
-// The exact score is the fma chain  acc = fma(u[s], i[s], acc); acc = fma(u[D/2 + s], i[D/2 + s], acc), s = 0 .. D/2 - 1 --
-// BIT-IDENTICAL to what v_mfma_f32_32x32x2_f32 accumulates in gemm_nt_kernel with its operand assignment (measured on
-// gfx950: tools/microbench/mfma_chain.hip, 40 / 40 tiles; every other order, 0 / 40), so ids and scores equal the plain
-// pipeline's bit for bit (tests/test_gpu_kernels.py compares them).  One workgroup per query row; rows whose list
-// overflowed are left alone.
+struct SurvivorBounds { float lower, width; };       // L_j and U_j - L_j
+// delta_j = cu |i_j| + slack shares: cu = c |u|; `slack` = kFilterAbsSlack |T| and the |sc| term cover the rounding of
+// s~ = (s~ - T) + T in the filter's hand-off.  L_j = sc - delta_j (rounded down by the slack's share), U_j = L_j + 2 delta_j.
+__device__ __forceinline__ SurvivorBounds survivor_bounds(float cu, float slack, float sc, float item_norm) {
+  const float dl = __builtin_fmaf(cu, item_norm, __builtin_fmaf(kFilterAbsSlack, fabsf(sc), slack));
+  return {sc - dl, 2.0f * dl};
+}
+// The exact score: the fma chain  acc = fma(u[s], i[s], acc); acc = fma(u[D/2 + s], i[D/2 + s], acc), s = 0 .. D/2 - 1 --
+// BIT-IDENTICAL to what v_mfma_f32_32x32x2_f32 accumulates in gemm_nt_kernel with its operand assignment (lane half h feeds
+// dimensions [h D/2, (h + 1) D/2), MFMA step s takes one from each half; measured on gfx950: tools/microbench/mfma_chain.hip,
+// 40 / 40 tiles; every other order, 0 / 40), so ids and scores equal the plain pipeline's bit for bit
+// (tests/test_gpu_ranking.py compares them).  THE one definition: both re-score kernels call it.
+template <int D>
+__device__ __forceinline__ float chain_score(const float* s_u, const float4* item_row) {
+  constexpr int DH = D / 2;
+  float acc = 0.f;
+#pragma unroll 4
+  for (int q = 0; q < DH / 4; ++q) {
+    const float4 x0 = item_row[q], x1 = item_row[DH / 4 + q];
+    acc = __builtin_fmaf(s_u[4 * q + 0], x0.x, acc); acc = __builtin_fmaf(s_u[DH + 4 * q + 0], x1.x, acc);
+    acc = __builtin_fmaf(s_u[4 * q + 1], x0.y, acc); acc = __builtin_fmaf(s_u[DH + 4 * q + 1], x1.y, acc);
+    acc = __builtin_fmaf(s_u[4 * q + 2], x0.z, acc); acc = __builtin_fmaf(s_u[DH + 4 * q + 2], x1.z, acc);
+    acc = __builtin_fmaf(s_u[4 * q + 3], x0.w, acc); acc = __builtin_fmaf(s_u[DH + 4 * q + 3], x1.w, acc);
+  }
+  return acc;
+}
+
+// One workgroup per query row; rows whose list overflowed are left alone.
 template <int D>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8))) void rescore_topk_kernel(const float* __restrict__ U, const int32_t* __restrict__ user_ids,
                                                            int user_base, const float* __restrict__ I,
@@ -566,7 +509,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8))) voi
                                                            const int32_t* __restrict__ r_indices,
                                                            int32_t* __restrict__ out_ids, float* __restrict__ out_scores,
                                                            int skip_upto) {
-  constexpr int DH = D / 2;
   extern __shared__ unsigned char cand_smem[];
   float* s_val = reinterpret_cast<float*>(cand_smem);         // approximate scores, then exact ones of the second round
   int* s_idx = reinterpret_cast<int*>(cand_smem) + cap;
@@ -579,7 +521,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8))) voi
   const int c = cnt[row];
   if (c > cap || c <= skip_upto) return;                       // (short lists: rescore_wave_kernel has ranked them)
   if (threadIdx.x == 0) { s_n = 0; s_m = 0; s_tau = -INFINITY; }
-  const int u = user_ids ? user_ids[row] : user_base + row;          // the user's id: mask CSR row
+  const int u = query_user(user_ids, user_base, row);          // the user's id: mask CSR row
   const int urow = user_ids ? u : row;
   if (threadIdx.x < D) s_u[threadIdx.x] = U[(size_t)urow * D + threadIdx.x];
   __syncthreads();
@@ -592,7 +534,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8))) voi
   // items) filled from the row with one coalesced pass -- a binary search per candidate is a chain of 6-7 dependent L2
   // round trips, ~10 us of this kernel's 40 per workgroup -- or the binary search for larger catalogues
   unsigned int* s_bits = reinterpret_cast<unsigned int*>(s_dl + cap);
-  // delta_j = cu |i_j| + slack: cu = c |u|; the slack covers the rounding of s~ = (s~ - T) + T in the filter's hand-off
   const float cu = kFilterMargin * u_norm[row];
   const float slack = kFilterAbsSlack * fabsf(thr[(size_t)row * thr_stride]);
   if (bitmap_words > 0) {
@@ -610,27 +551,18 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8))) voi
     int id = 0;
     if (keep) {
       id = cand_id[(size_t)row * cap + t];
-      if (bitmap_words > 0) {
-        keep = !((s_bits[id >> 5] >> (id & 31)) & 1u);
-      } else {
-        int lo = rs, hi = re;
-        while (lo < hi) {
-          const int mid = (lo + hi) >> 1;
-          if (r_indices[mid] < id) lo = mid + 1; else hi = mid;
-        }
-        keep = !(lo < re && r_indices[lo] == id);
-      }
+      if (bitmap_words > 0) keep = !((s_bits[id >> 5] >> (id & 31)) & 1u);
+      else keep = !sorted_contains(r_indices, rs, re, id);
     }
     const unsigned long long bal = __builtin_amdgcn_ballot_w64(keep);
     int base = 0;
     if (lane == 0 && bal) base = atomicAdd(&s_n, __builtin_popcountll(bal));
     base = __builtin_amdgcn_readfirstlane(base);
     if (keep) {
-      const int at = base + __builtin_amdgcn_mbcnt_hi((unsigned)(bal >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bal, 0));
-      const float sc = cand_sc[(size_t)row * cap + t];
-      const float dl = __builtin_fmaf(cu, item_norm[id], __builtin_fmaf(kFilterAbsSlack, fabsf(sc), slack));
-      s_val[at] = sc - dl;                                     // L_j (rounded down by the slack's share)
-      s_dl[at] = 2.0f * dl;                                    // U_j = L_j + 2 delta_j
+      const int at = base + lane_rank(bal);
+      const SurvivorBounds b = survivor_bounds(cu, slack, cand_sc[(size_t)row * cap + t], item_norm[id]);
+      s_val[at] = b.lower;
+      s_dl[at] = b.width;
       s_idx[at] = id;
     }
   }
@@ -641,7 +573,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8))) voi
     const float v = s_val[t];
     const int id = s_idx[t];
     int rank = 0;
-    for (int j = 0; j < nv; ++j) rank += (s_val[j] > v) || (s_val[j] == v && s_idx[j] < id);
+    for (int j = 0; j < nv; ++j) rank += before(s_val[j], s_idx[j], v, id);
     if (rank == min(k, nv) - 1) s_tau = (nv >= k) ? v : -INFINITY;
   }
   __syncthreads();
@@ -653,24 +585,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8))) voi
     int base = 0;
     if (lane == 0 && bal) base = atomicAdd(&s_m, __builtin_popcountll(bal));
     base = __builtin_amdgcn_readfirstlane(base);
-    if (keep) s_sel[base + __builtin_amdgcn_mbcnt_hi((unsigned)(bal >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bal, 0))] = t;
+    if (keep) s_sel[base + lane_rank(bal)] = t;
   }
   __syncthreads();
   const int ns = s_m;
   // exact scores of the second round, in place
   for (int e = threadIdx.x; e < ns; e += 256) {
     const int t = s_sel[e];
-    const float4* ip = reinterpret_cast<const float4*>(I + (size_t)s_idx[t] * D);
-    float acc = 0.f;
-#pragma unroll 4
-    for (int q = 0; q < DH / 4; ++q) {
-      const float4 x0 = ip[q], x1 = ip[DH / 4 + q];
-      acc = __builtin_fmaf(s_u[4 * q + 0], x0.x, acc); acc = __builtin_fmaf(s_u[DH + 4 * q + 0], x1.x, acc);
-      acc = __builtin_fmaf(s_u[4 * q + 1], x0.y, acc); acc = __builtin_fmaf(s_u[DH + 4 * q + 1], x1.y, acc);
-      acc = __builtin_fmaf(s_u[4 * q + 2], x0.z, acc); acc = __builtin_fmaf(s_u[DH + 4 * q + 2], x1.z, acc);
-      acc = __builtin_fmaf(s_u[4 * q + 3], x0.w, acc); acc = __builtin_fmaf(s_u[DH + 4 * q + 3], x1.w, acc);
-    }
-    s_val[t] = acc;
+    s_val[t] = chain_score<D>(s_u, reinterpret_cast<const float4*>(I + (size_t)s_idx[t] * D));
   }
   __syncthreads();
   for (int e = threadIdx.x; e < ns; e += 256) {
@@ -680,7 +602,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8))) voi
     int rank = 0;
     for (int j = 0; j < ns; ++j) {
       const int tj = s_sel[j];
-      rank += (s_val[tj] > v) || (s_val[tj] == v && s_idx[tj] < id);
+      rank += before(s_val[tj], s_idx[tj], v, id);
     }
     if (rank < k) {
       out_ids[(size_t)row * k + rank] = id;
@@ -694,7 +616,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8))) voi
 // 20 us per row are a chain of dependent round trips with seven rows in flight per CU.  Here a row is a wave: no barrier
 // (a wave's LDS operations complete in order), the counters of the compactions are wave-uniform registers, membership in
 // the user's training row is a binary search in an LDS copy of that row (rows longer than TRW: in global memory), and
-// 24 rows are in flight per CU.  Same arithmetic, same order of the exact fma chain, same (score desc, id asc) ranking.
+// 24 rows are in flight per CU.  Same survivor_bounds, same chain_score, same (score desc, id asc) ranking.
 // A list is this kernel's only if it is short AND complete: c <= min(CW, cap).  With cap < CW (the API allows any
 // k <= cap <= 4096) a row with cap < c <= CW has overflowed -- slots t >= cap were never written and the words there belong
 // to the next row or to nobody -- and is left alone, reported through its count, like everywhere else.  (The first version
@@ -710,7 +632,7 @@ __global__ __launch_bounds__(256) void rescore_wave_kernel(const float* __restri
                                                            const float* __restrict__ thr, int thr_stride, int cap, int k,
                                                            const int32_t* __restrict__ r_indptr, const int32_t* __restrict__ r_indices,
                                                            int32_t* __restrict__ out_ids, float* __restrict__ out_scores) {
-  constexpr int DH = D / 2, TRW = 512;
+  constexpr int TRW = 512;
   __shared__ float s_val_[4][CW];
   __shared__ float s_dl_[4][CW];
   __shared__ int s_idx_[4][CW];
@@ -728,7 +650,7 @@ __global__ __launch_bounds__(256) void rescore_wave_kernel(const float* __restri
   short* s_sel = s_sel_[w];
   int* s_tr = s_tr_[w];
   float* s_u = s_u_[w];
-  const int u = user_ids ? user_ids[row] : user_base + row;
+  const int u = query_user(user_ids, user_base, row);
   const int urow = user_ids ? u : row;
   for (int q = lane; q < D; q += 64) s_u[q] = U[(size_t)urow * D + q];
   const int rs = r_indptr ? r_indptr[u] : 0, re = r_indptr ? r_indptr[u + 1] : 0;
@@ -746,28 +668,14 @@ __global__ __launch_bounds__(256) void rescore_wave_kernel(const float* __restri
     int id = 0;
     if (keep) {
       id = cand_id[(size_t)row * cap + t];
-      int lo = 0, hi = ntr;
-      if (cached) {
-        while (lo < hi) {
-          const int mid = (lo + hi) >> 1;
-          if (s_tr[mid] < id) lo = mid + 1; else hi = mid;
-        }
-        keep = !(lo < ntr && s_tr[lo] == id);
-      } else {
-        while (lo < hi) {
-          const int mid = (lo + hi) >> 1;
-          if (r_indices[rs + mid] < id) lo = mid + 1; else hi = mid;
-        }
-        keep = !(lo < ntr && r_indices[rs + lo] == id);
-      }
+      keep = cached ? !sorted_contains(s_tr, 0, ntr, id) : !sorted_contains(r_indices, rs, re, id);
     }
     const unsigned long long bal = __builtin_amdgcn_ballot_w64(keep);
     if (keep) {
-      const int at = nv + __builtin_amdgcn_mbcnt_hi((unsigned)(bal >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bal, 0));
-      const float sc = cand_sc[(size_t)row * cap + t];
-      const float dl = __builtin_fmaf(cu, item_norm[id], __builtin_fmaf(kFilterAbsSlack, fabsf(sc), slack));
-      s_val[at] = sc - dl;
-      s_dl[at] = 2.0f * dl;
+      const int at = nv + lane_rank(bal);
+      const SurvivorBounds b = survivor_bounds(cu, slack, cand_sc[(size_t)row * cap + t], item_norm[id]);
+      s_val[at] = b.lower;
+      s_dl[at] = b.width;
       s_idx[at] = id;
     }
     nv += __builtin_popcountll(bal);
@@ -784,7 +692,7 @@ __global__ __launch_bounds__(256) void rescore_wave_kernel(const float* __restri
         v = s_val[t];
         const int id = s_idx[t];
         int rank = 0;
-        for (int j = 0; j < nv; ++j) rank += (s_val[j] > v) || (s_val[j] == v && s_idx[j] < id);
+        for (int j = 0; j < nv; ++j) rank += before(s_val[j], s_idx[j], v, id);
         hit = rank == k - 1;
       }
       const unsigned long long bal = __builtin_amdgcn_ballot_w64(hit);
@@ -797,24 +705,14 @@ __global__ __launch_bounds__(256) void rescore_wave_kernel(const float* __restri
     const int t = t0 + lane;
     const bool keep = t < nv && s_val[t] + s_dl[t] >= tau;
     const unsigned long long bal = __builtin_amdgcn_ballot_w64(keep);
-    if (keep) s_sel[ns + __builtin_amdgcn_mbcnt_hi((unsigned)(bal >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bal, 0))] = (short)t;
+    if (keep) s_sel[ns + lane_rank(bal)] = (short)t;
     ns += __builtin_popcountll(bal);
   }
   __builtin_amdgcn_wave_barrier();
-  // 4. their exact scores, in place: a lane per candidate, the fma chain of gemm_nt_kernel's MFMA in its order
+  // 4. their exact scores, in place: a lane per candidate
   for (int e = lane; e < ns; e += 64) {
     const int t = s_sel[e];
-    const float4* ip = reinterpret_cast<const float4*>(I + (size_t)s_idx[t] * D);
-    float acc = 0.f;
-#pragma unroll 4
-    for (int q = 0; q < DH / 4; ++q) {
-      const float4 x0 = ip[q], x1 = ip[DH / 4 + q];
-      acc = __builtin_fmaf(s_u[4 * q + 0], x0.x, acc); acc = __builtin_fmaf(s_u[DH + 4 * q + 0], x1.x, acc);
-      acc = __builtin_fmaf(s_u[4 * q + 1], x0.y, acc); acc = __builtin_fmaf(s_u[DH + 4 * q + 1], x1.y, acc);
-      acc = __builtin_fmaf(s_u[4 * q + 2], x0.z, acc); acc = __builtin_fmaf(s_u[DH + 4 * q + 2], x1.z, acc);
-      acc = __builtin_fmaf(s_u[4 * q + 3], x0.w, acc); acc = __builtin_fmaf(s_u[DH + 4 * q + 3], x1.w, acc);
-    }
-    s_val[t] = acc;
+    s_val[t] = chain_score<D>(s_u, reinterpret_cast<const float4*>(I + (size_t)s_idx[t] * D));
   }
   __builtin_amdgcn_wave_barrier();
   // 5. (score desc, id asc) among them
@@ -825,7 +723,7 @@ __global__ __launch_bounds__(256) void rescore_wave_kernel(const float* __restri
     int rank = 0;
     for (int j = 0; j < ns; ++j) {
       const int tj = s_sel[j];
-      rank += (s_val[tj] > v) || (s_val[tj] == v && s_idx[tj] < id);
+      rank += before(s_val[tj], s_idx[tj], v, id);
     }
     if (rank < k) {
       out_ids[(size_t)row * k + rank] = id;
@@ -872,7 +770,7 @@ __global__ __launch_bounds__(256) void bound_rows_kernel(float* __restrict__ sco
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= rows) return;
   if (mask_indptr) {
-    const int u = user_ids ? user_ids[row] : user_base + row;
+    const int u = query_user(user_ids, user_base, row);
     const int ms = mask_indptr[u], me = mask_indptr[u + 1];
     for (int p = ms + lane; p < me; p += 64) {
       const int item = column_of_item[mask_indices[p]];           // (the slab's columns are image rows: items by norm)
@@ -907,10 +805,6 @@ __global__ __launch_bounds__(256) void bound_rows_kernel(float* __restrict__ sco
 
 constexpr int kTopkThreads = 256;
 constexpr int kTopkCap = 2048;
-
-__device__ __forceinline__ bool before(float sa, int ia, float sb, int ib) {
-  return (sa > sb) || (sa == sb && ia < ib);
-}
 
 __global__ __launch_bounds__(kTopkThreads) void topk_kernel(const float* __restrict__ scores, int rows, int n, int k,
                                                             int32_t* __restrict__ out_ids, float* __restrict__ out_scores) {
@@ -1076,12 +970,7 @@ __global__ __launch_bounds__(256) void hit_flags_kernel(const int32_t* __restric
   const int64_t q = t / k;
   const int u = user_ids ? user_ids[q] : (int)q;
   const int item = ids[t];
-  int lo = t_indptr[u], hi = t_indptr[u + 1];
-  while (lo < hi) {
-    const int mid = (lo + hi) >> 1;
-    if (t_indices[mid] < item) lo = mid + 1; else hi = mid;
-  }
-  flags[t] = (lo < t_indptr[u + 1] && t_indices[lo] == item) ? 1 : 0;
+  flags[t] = sorted_contains(t_indices, t_indptr[u], t_indptr[u + 1], item) ? 1 : 0;
 }
 // (f-3) per-user hits and DCG / IDCG at up to 8 cut-offs: one thread per user, float64 adds in position order (the adds
 // of Metric.NDCG's generator sum; a non-hit adds nothing there and +0.0 here)
@@ -1107,6 +996,198 @@ __global__ __launch_bounds__(256) void metric_rows_kernel(const uint8_t* __restr
     ndcg[(size_t)c * n_query + q] = dcg / ideal[(size_t)c * (k + 1) + min(size, cuts.cut[c])];
   }
 }
+
+// ---------------------------------------------------------------------------------------
+// The filtered ranking on the host: ONE workspace layout, two pipelines.
+// ---------------------------------------------------------------------------------------
+// Byte offsets of every array of srh_score_mask_topk_filtered's workspace; each starts on a 256-byte boundary.  The sizing
+// call returns `total`, the entry point takes every pointer from here.
+inline bool filt_split_served(int32_t d) { return d == 64 || d == 128; }
+struct FiltLayout {
+  // both pipelines, per chunk of query rows
+  int64_t slab;                // (rows, sample) f32: the scores of the bound slice
+  int64_t s_ids, s_sc;         // (rows, k): the slice's ranked ids (f32 pipeline only) and scores; column k - 1 = the bound
+  int64_t cand_id, cand_sc;    // (rows, cap): the survivor lists
+  // the bf16 pipeline (d = 64 / 128); `padded` = the catalogue in whole 32-item tiles
+  int64_t i_img;               // (padded, d) bf16: the item image, fragment-linear, in norm order
+  int64_t u_img, u_norm;       // (rows, d) bf16, (rows) f32: the chunk's query rows
+  int64_t i_norm;              // (padded) f32: norms by image row
+  int64_t norm_bits, sorted_bits, iota, order, column_of_item;    // (padded) x 4 bytes each: the norm order (norm_bits = norms by ITEM)
+  int64_t sort_temp, sort_bytes;                                   // hipcub's scratch and its unaligned size
+  int64_t total;
+};
+FiltLayout filt_layout(int64_t rows, int64_t sample, int32_t k, int32_t cap, int64_t n_items, int32_t d) {
+  FiltLayout L{};
+  int64_t at = 0;
+  auto take = [&at](int64_t bytes) { const int64_t o = at; at += align256(bytes); return o; };
+  L.slab = take(4 * rows * sample);
+  L.s_ids = take(4 * rows * k);
+  L.s_sc = take(4 * rows * k);
+  L.cand_id = take(4 * rows * cap);
+  L.cand_sc = take(4 * rows * cap);
+  if (filt_split_served(d)) {
+    const int64_t padded = (n_items + 31) / 32 * 32;
+    L.i_img = take(2 * padded * d);
+    L.u_img = take(2 * rows * d);
+    L.u_norm = take(4 * rows);
+    L.i_norm = take(4 * padded);
+    L.norm_bits = take(4 * padded);
+    L.sorted_bits = take(4 * padded);
+    L.iota = take(4 * padded);
+    L.order = take(4 * padded);
+    L.column_of_item = take(4 * padded);
+    L.sort_bytes = (int64_t)filt_sort_temp_bytes(n_items);
+    L.sort_temp = take(L.sort_bytes);
+  }
+  L.total = at;
+  return L;
+}
+
+// the entry point's arguments, validated, as both pipelines take them
+struct FiltCall {
+  const float* user_emb; const int32_t* user_ids; int64_t n_query;
+  const float* item_emb; int64_t n_items;
+  const int32_t* r_indptr; const int32_t* r_indices;
+  int32_t k; int64_t sample_items; int32_t cap; int64_t chunk_rows;
+  char* ws;
+  int32_t* out_ids; float* out_scores; int32_t* out_counts;
+  hipStream_t st;
+  template <typename T> T* at(int64_t offset) const { return reinterpret_cast<T*>(ws + offset); }
+};
+#define SRH_FILT_HIP(call, what)                                                        \
+  do {                                                                                  \
+    hipError_t e_ = (call);                                                             \
+    if (e_ != hipSuccess) {                                                             \
+      srh::set_error("score_mask_topk_filtered: " what "%s", hipGetErrorString(e_));    \
+      return SRH_ERR_HIP;                                                               \
+    }                                                                                   \
+  } while (0)
+
+// Exact f32 scores throughout (d = 32 / 256).  Per chunk:
+//   1. top-K over a leading slice of the catalogue: its K-th score is a lower bound of the row's overall K-th score (a
+//      subset's K-th best cannot beat the whole set's);
+//   2. all scores again, never stored: only those reaching the bound are kept;
+//   3. training items dropped, exact order of the survivors.
+srh_status_t filt_f32_pipeline(const FiltCall& a, const FiltLayout& L, int32_t d) {
+  float* slab = a.at<float>(L.slab);
+  int32_t* s_ids = a.at<int32_t>(L.s_ids);
+  float* s_sc = a.at<float>(L.s_sc);
+  int32_t* cand_id = a.at<int32_t>(L.cand_id);
+  float* cand_sc = a.at<float>(L.cand_sc);
+  const int32_t k = a.k;
+  for (int64_t lo = 0; lo < a.n_query; lo += a.chunk_rows) {
+    const int64_t m = std::min(a.chunk_rows, a.n_query - lo);
+    const float* emb = a.user_ids ? a.user_emb : a.user_emb + lo * d;
+    const int32_t* ids = a.user_ids ? a.user_ids + lo : nullptr;
+    int32_t* cnt = a.out_counts + lo;
+    srh_status_t rc = gemm_dispatch(emb, ids, a.item_emb, slab, m, a.sample_items, d, a.st);
+    if (rc) return rc;
+    if (a.r_indptr) {
+      mask_kernel<<<(int)((m + 3) / 4), 256, 0, a.st>>>(ids, (int)m, a.r_indptr, a.r_indices, slab, (int)a.sample_items, (int)lo);
+      SRH_LAUNCH_CHECK();
+    }
+    rc = srh_topk_rows(slab, m, a.sample_items, k, s_ids, s_sc, a.st);
+    if (rc) return rc;
+    SRH_FILT_HIP(hipMemsetAsync(cnt, 0, sizeof(int32_t) * m, a.st), "");
+    FilterArgs fa{s_sc + (k - 1), k, cnt, cand_id, cand_sc, a.cap};
+    rc = gemm_dispatch(emb, ids, a.item_emb, nullptr, m, a.n_items, d, a.st, &fa);
+    if (rc) return rc;
+    cand_topk_kernel<<<(int)m, 256, (size_t)a.cap * 8, a.st>>>(cnt, cand_id, cand_sc, a.cap, k, ids, (int)lo, a.r_indptr, a.r_indices,
+                                                               a.out_ids + lo * k, a.out_scores + lo * k);
+    SRH_LAUNCH_CHECK();
+  }
+  return SRH_OK;
+}
+
+// filter16_kernel's grid: 256 query rows per workgroup; the item tiles are dealt over enough workgroups to give every CU two
+dim3 filter16_grid(int64_t m, int64_t n) {
+  const int tiles = (int)((n + 31) / 32);
+  const int gy = (int)((m + 255) / 256);
+  const int gx = std::max(1, std::min(tiles, (512 + gy - 1) / gy));
+  const int tiles_per_wg = (tiles + gx - 1) / gx;
+  return dim3((unsigned)((tiles + tiles_per_wg - 1) / tiles_per_wg), (unsigned)gy);
+}
+
+// The bf16 filter (d = 64 / 128).  Once per ranking: the catalogue in norm order, largest first (see item_norms_kernel), and
+// its operand image in that order.  Per chunk:
+//   1. the query rows' image; bf16 scores s~ - delta of the bound slice (the `sample_items` items of largest norm) into the
+//      slab; the bound: one pass, one wave per row, the row's masks applied by the same wave -- the K-th largest exact score
+//      is >= the K-th largest s~ - delta;
+//   2. the filter on bf16 operands against that bound, widened by each score's own margin;
+//   3. the survivors re-scored by gemm_nt_kernel's own instruction sequence, masked, ranked: short lists (all but a few per
+//      cent of the rows) by a wave each, the rest by a workgroup each.
+template <int D>
+srh_status_t filt_split_pipeline(const FiltCall& a, const FiltLayout& L) {
+  constexpr int LPR = D / 4, G = 64 / LPR;
+  constexpr int kWaveRows = 128;               // (longer lists: the O(n^2) rank counts want the 256 threads of the workgroup form)
+  hipStream_t st = a.st;
+  float* slab = a.at<float>(L.slab);
+  float* bound = a.at<float>(L.s_sc) + (a.k - 1);       // row r's bound at bound[r * k]
+  int32_t* cand_id = a.at<int32_t>(L.cand_id);
+  float* cand_sc = a.at<float>(L.cand_sc);
+  uint16_t* i_img = a.at<uint16_t>(L.i_img);
+  uint16_t* u_img = a.at<uint16_t>(L.u_img);
+  float* u_norm = a.at<float>(L.u_norm);
+  float* i_norm = a.at<float>(L.i_norm);
+  uint32_t* norm_bits = a.at<uint32_t>(L.norm_bits);
+  const float* norm_by_item = a.at<const float>(L.norm_bits);
+  int32_t* iota = a.at<int32_t>(L.iota);
+  int32_t* order = a.at<int32_t>(L.order);
+  int32_t* column_of_item = a.at<int32_t>(L.column_of_item);
+  const int32_t k = a.k, cap = a.cap;
+  const int64_t n_items = a.n_items, padded = (n_items + 31) / 32 * 32;
+  // (the last tile's rows beyond the catalogue: norm 0 -- their scores are never looked at)
+  if (padded > n_items) SRH_FILT_HIP(hipMemsetAsync(i_norm + n_items, 0, sizeof(float) * (size_t)(padded - n_items), st), "");
+  const int item_blocks = (int)(((n_items + G - 1) / G + 3) / 4);
+  item_norms_kernel<LPR><<<item_blocks, 256, 0, st>>>(a.item_emb, (int)n_items, norm_bits, iota);
+  SRH_LAUNCH_CHECK();
+  size_t sort_bytes = (size_t)L.sort_bytes;
+  SRH_FILT_HIP(hipcub::DeviceRadixSort::SortPairsDescending(a.at<void>(L.sort_temp), sort_bytes, norm_bits, a.at<uint32_t>(L.sorted_bits),
+                                                            iota, order, (int)n_items, 0, 32, st), "sort: ");
+  invert_order_kernel<<<(int)((n_items + 255) / 256), 256, 0, st>>>(order, (int)n_items, column_of_item);
+  SRH_LAUNCH_CHECK();
+  split_rows_kernel<LPR, true><<<item_blocks, 256, 0, st>>>(a.item_emb, order, (int)n_items, i_img, i_norm);
+  SRH_LAUNCH_CHECK();
+  static const bool attr_set = [] {
+    (void)hipFuncSetAttribute((const void*)filter16_kernel<D, false>, hipFuncAttributeMaxDynamicSharedMemorySize, kF16Lds);
+    (void)hipFuncSetAttribute((const void*)filter16_kernel<D, true>, hipFuncAttributeMaxDynamicSharedMemorySize, kF16Lds);
+    return true;
+  }();
+  (void)attr_set;
+  // (training-row membership in rescore_topk_kernel by an LDS bitmap over the catalogue while it fits: <= 16 KB, i.e. 131 k items)
+  const int bitmap_words = (a.r_indptr && n_items <= 131072) ? (int)((n_items + 31) / 32) : 0;
+  const size_t rs_lds = (size_t)cap * 16 + (size_t)bitmap_words * 4;
+  for (int64_t lo = 0; lo < a.n_query; lo += a.chunk_rows) {
+    const int64_t m = std::min(a.chunk_rows, a.n_query - lo);
+    const float* emb = a.user_ids ? a.user_emb : a.user_emb + lo * D;
+    const int32_t* ids = a.user_ids ? a.user_ids + lo : nullptr;
+    int32_t* cnt = a.out_counts + lo;
+    int32_t* out_ids = a.out_ids + lo * k;
+    float* out_scores = a.out_scores + lo * k;
+    const int row_waves = (int)((m + 3) / 4);             // workgroups of a one-wave-per-row launch
+    split_rows_kernel<LPR, false><<<(int)(((m + G - 1) / G + 3) / 4), 256, 0, st>>>(emb, ids, (int)m, u_img, u_norm);
+    Filter16Args none{};
+    none.u_norm = u_norm;
+    none.item_norm = i_norm;
+    none.order = order;
+    filter16_kernel<D, true><<<filter16_grid(m, a.sample_items), 64 * kF16Waves, kF16Lds, st>>>(u_img, i_img, (int)m, (int)a.sample_items, none, slab);
+    SRH_LAUNCH_CHECK();
+    bound_rows_kernel<<<row_waves, 256, 0, st>>>(slab, (int)m, (int)a.sample_items, k, bound, k, ids, (int)lo,
+                                                 a.r_indptr, a.r_indices, column_of_item);
+    SRH_LAUNCH_CHECK();
+    SRH_FILT_HIP(hipMemsetAsync(cnt, 0, sizeof(int32_t) * m, st), "");
+    Filter16Args f16{bound, k, u_norm, i_norm, order, cnt, cand_id, cand_sc, cap};
+    filter16_kernel<D, false><<<filter16_grid(m, n_items), 64 * kF16Waves, kF16Lds, st>>>(u_img, i_img, (int)m, (int)n_items, f16);
+    SRH_LAUNCH_CHECK();
+    rescore_wave_kernel<D, kWaveRows><<<row_waves, 256, 0, st>>>(emb, ids, (int)lo, a.item_emb, (int)m, cnt, cand_id, cand_sc, u_norm,
+                                                                 norm_by_item, bound, k, cap, k, a.r_indptr, a.r_indices, out_ids, out_scores);
+    rescore_topk_kernel<D><<<(int)m, 256, rs_lds, st>>>(emb, ids, (int)lo, a.item_emb, cnt, cand_id, cand_sc, u_norm, norm_by_item,
+                                                        bound, k, cap, k, bitmap_words, a.r_indptr, a.r_indices, out_ids, out_scores, kWaveRows);
+    SRH_LAUNCH_CHECK();
+  }
+  return SRH_OK;
+}
+#undef SRH_FILT_HIP
 }  // namespace
 
 extern "C" {
@@ -1171,26 +1252,15 @@ srh_status_t srh_score_mask_topk(const float* d_user_emb, const int32_t* d_user_
   return SRH_OK;
 }
 
-// Layout of one user chunk in the workspace of the filtered ranking
-static inline int64_t filt_align(int64_t b) { return (b + 255) / 256 * 256; }
-static int64_t filt_chunk_bytes(int64_t rows, int64_t sample, int32_t k, int32_t cap) {
-  return filt_align(rows * sample * 4) + 2 * filt_align(rows * k * 4) + filt_align(rows * 4) + 2 * filt_align(rows * (int64_t)cap * 4);
-}
-// the split-bf16 filter's share: hi / lo images of the item table and of one chunk of query rows, their norms
-static bool filt_split_served(int32_t d) { return d == 64 || d == 128; }
-static int64_t filt_split_bytes(int64_t rows, int64_t n_items, int32_t d) {
-  if (!filt_split_served(d)) return 0;
-  const int64_t padded = (n_items + 31) / 32 * 32;               // the item images are whole 32-row tiles
-  // + the norm order of the catalogue: norms by item (the sort's keys), sorted keys, 0 .. n-1, the order, its inverse, the
-  //   sort's scratch
-  return 2 * filt_align(padded * d * 2) + 2 * filt_align(rows * d * 2) + filt_align(rows * 4) + filt_align(padded * 4) +
-         5 * filt_align(padded * 4) + filt_align((int64_t)filt_sort_temp_bytes(n_items));
-}
-
+// The workspace of srh_score_mask_topk_filtered in closed form (filt_layout is the one place that spells it out), with
+// A(x) = ceil(x / 256) * 256, rows = chunk_rows, padded = ceil(n_items / 32) * 32:
+//   every d:       A(4 rows sample) + 2 A(4 rows k) + 2 A(4 rows cap)
+//   d = 64 / 128:  + A(2 padded d) + A(2 rows d) + A(4 rows) + 6 A(4 padded) + A(hipcub's radix-sort scratch for n_items pairs)
+// 0 for a non-positive argument.
 int64_t srh_score_mask_topk_filtered_ws_bytes(int64_t chunk_rows, int64_t sample_items, int32_t k, int32_t cap,
                                               int64_t n_items, int32_t d) {
   if (chunk_rows <= 0 || sample_items <= 0 || k <= 0 || cap <= 0 || n_items <= 0 || d <= 0) return 0;
-  return filt_chunk_bytes(chunk_rows, sample_items, k, cap) + filt_split_bytes(chunk_rows, n_items, d);
+  return filt_layout(chunk_rows, sample_items, k, cap, n_items, d).total;
 }
 
 srh_status_t srh_score_mask_topk_filtered(const float* d_user_emb, const int32_t* d_user_ids, int64_t n_query,
@@ -1203,157 +1273,12 @@ srh_status_t srh_score_mask_topk_filtered(const float* d_user_emb, const int32_t
   SRH_REQUIRE(n_query > 0 && n_items > 0 && chunk_rows > 0, "score_mask_topk_filtered: bad shape");
   SRH_REQUIRE(k >= 1 && k <= 128 && sample_items >= k && sample_items <= n_items && cap >= k && cap <= 4096,
               "score_mask_topk_filtered: need k <= sample_items <= n_items and k <= cap <= 4096");
-  hipStream_t st = srh::as_stream(stream);
-  char* ws = reinterpret_cast<char*>(d_ws);
-  float* slab = reinterpret_cast<float*>(ws); ws += filt_align(chunk_rows * sample_items * 4);
-  int32_t* s_ids = reinterpret_cast<int32_t*>(ws); ws += filt_align(chunk_rows * k * 4);
-  float* s_sc = reinterpret_cast<float*>(ws); ws += filt_align(chunk_rows * k * 4);
-  int32_t* cand_id = reinterpret_cast<int32_t*>(ws); ws += filt_align(chunk_rows * (int64_t)cap * 4);
-  float* cand_sc = reinterpret_cast<float*>(ws); ws += filt_align(chunk_rows * (int64_t)cap * 4);
-  // split-bf16 filter (d = 64 / 128): operand images of the whole item table once, of each chunk's query rows per chunk
-  const bool split = filt_split_served(d);
-  uint16_t *i_hi = nullptr, *i_lo = nullptr, *u_hi = nullptr, *u_lo = nullptr;
-  float *u_norm = nullptr, *i_norm = nullptr;
-  const float* norm_by_item = nullptr;
-  int32_t *order = nullptr, *column_of_item = nullptr;
-  if (split) {
-    ws += filt_align(chunk_rows * 4);            // (the chunk layout's counter slot: counts live in d_out_counts)
-    const int64_t padded = (n_items + 31) / 32 * 32;
-    i_hi = reinterpret_cast<uint16_t*>(ws); ws += 2 * filt_align(padded * d * 2);      // hi and lo fragments, tile by tile
-    i_lo = nullptr;
-    u_hi = reinterpret_cast<uint16_t*>(ws); ws += filt_align(chunk_rows * d * 2);
-    u_lo = reinterpret_cast<uint16_t*>(ws); ws += filt_align(chunk_rows * d * 2);
-    u_norm = reinterpret_cast<float*>(ws); ws += filt_align(chunk_rows * 4);
-    i_norm = reinterpret_cast<float*>(ws); ws += filt_align(padded * 4);
-    uint32_t* norm_bits = reinterpret_cast<uint32_t*>(ws); ws += filt_align(padded * 4);       // = norms by ITEM, as floats
-    uint32_t* sorted_bits = reinterpret_cast<uint32_t*>(ws); ws += filt_align(padded * 4);
-    int32_t* iota = reinterpret_cast<int32_t*>(ws); ws += filt_align(padded * 4);
-    order = reinterpret_cast<int32_t*>(ws); ws += filt_align(padded * 4);
-    column_of_item = reinterpret_cast<int32_t*>(ws); ws += filt_align(padded * 4);
-    void* sort_temp = ws;
-    size_t sort_bytes = filt_sort_temp_bytes(n_items);
-    norm_by_item = reinterpret_cast<const float*>(norm_bits);
-    // (the last tile's rows beyond the catalogue: norm 0 -- their scores are never looked at)
-    hipError_t err = padded > n_items ? hipMemsetAsync(i_norm + n_items, 0, sizeof(float) * (size_t)(padded - n_items), st) : hipSuccess;
-    if (err != hipSuccess) { srh::set_error("score_mask_topk_filtered: %s", hipGetErrorString(err)); return SRH_ERR_HIP; }
-    const int lpr = d / 4, g = 64 / lpr;
-    const int blocks = (int)(((n_items + g - 1) / g + 3) / 4);
-    // the catalogue in norm order, largest first (see item_norms_kernel), then its operand image in that order
-    if (d == 64) item_norms_kernel<16><<<blocks, 256, 0, st>>>(d_item_emb, (int)n_items, norm_bits, iota);
-    else item_norms_kernel<32><<<blocks, 256, 0, st>>>(d_item_emb, (int)n_items, norm_bits, iota);
-    SRH_LAUNCH_CHECK();
-    err = hipcub::DeviceRadixSort::SortPairsDescending(sort_temp, sort_bytes, norm_bits, sorted_bits, iota, order, (int)n_items, 0, 32, st);
-    if (err != hipSuccess) { srh::set_error("score_mask_topk_filtered: sort: %s", hipGetErrorString(err)); return SRH_ERR_HIP; }
-    invert_order_kernel<<<(int)((n_items + 255) / 256), 256, 0, st>>>(order, (int)n_items, column_of_item);
-    SRH_LAUNCH_CHECK();
-    if (d == 64) split_rows_kernel<16, true><<<blocks, 256, 0, st>>>(d_item_emb, order, (int)n_items, i_hi, i_lo, i_norm, nullptr);
-    else split_rows_kernel<32, true><<<blocks, 256, 0, st>>>(d_item_emb, order, (int)n_items, i_hi, i_lo, i_norm, nullptr);
-    SRH_LAUNCH_CHECK();
-    static const bool attr_set = [] {
-      (void)hipFuncSetAttribute((const void*)filter16_kernel<64, false, SRH_F16_UB>, hipFuncAttributeMaxDynamicSharedMemorySize, kF16Lds);
-      (void)hipFuncSetAttribute((const void*)filter16_kernel<128, false, SRH_F16_UB>, hipFuncAttributeMaxDynamicSharedMemorySize, kF16Lds);
-      (void)hipFuncSetAttribute((const void*)filter16_kernel<64, true, SRH_F16_UB>, hipFuncAttributeMaxDynamicSharedMemorySize, kF16Lds);
-      (void)hipFuncSetAttribute((const void*)filter16_kernel<128, true, SRH_F16_UB>, hipFuncAttributeMaxDynamicSharedMemorySize, kF16Lds);
-      return true;
-    }();
-    (void)attr_set;
-  }
-  for (int64_t lo = 0; lo < n_query; lo += chunk_rows) {
-    const int64_t m = std::min(chunk_rows, n_query - lo);
-    const float* emb = d_user_ids ? d_user_emb : d_user_emb + lo * d;
-    const int32_t* ids = d_user_ids ? d_user_ids + lo : nullptr;
-    int32_t* cnt = d_out_counts + lo;
-    // 1. top-K over a leading slice of the catalogue: its K-th score is a lower bound of the
-    //    row's overall K-th score (a subset's K-th best cannot beat the whole set's).  Exact f32 scores, or (split path)
-    //    split-bf16 scores s~: the K-th largest exact score is >= the K-th largest s~ - delta_u, which the filter accounts for
-    srh_status_t rc = SRH_OK;
-    if (split) {
-      const int lpr = d / 4, g = 64 / lpr;
-      const int sb = (int)(((m + g - 1) / g + 3) / 4);
-      const int s_tiles = (int)((sample_items + 31) / 32);
-      const int gy = (int)((m + 255) / 256);
-      const int gx = std::max(1, std::min(s_tiles, (512 + gy - 1) / gy));
-      const int tpw = (s_tiles + gx - 1) / gx;
-      dim3 grid((unsigned)((s_tiles + tpw - 1) / tpw), (unsigned)gy);
-      Filter16Args none{};
-      none.u_norm = u_norm;
-      none.item_norm = i_norm;
-      none.order = order;
-      if (d == 64) {
-        split_rows_kernel<16, false><<<sb, 256, 0, st>>>(emb, ids, (int)m, u_hi, u_lo, u_norm, nullptr);
-        filter16_kernel<64, true, SRH_F16_UB><<<grid, 512 / SRH_F16_UB, kF16Lds, st>>>(u_hi, u_lo, i_hi, (int)m, (int)sample_items, none, slab);
-      } else {
-        split_rows_kernel<32, false><<<sb, 256, 0, st>>>(emb, ids, (int)m, u_hi, u_lo, u_norm, nullptr);
-        filter16_kernel<128, true, SRH_F16_UB><<<grid, 512 / SRH_F16_UB, kF16Lds, st>>>(u_hi, u_lo, i_hi, (int)m, (int)sample_items, none, slab);
-      }
-      SRH_LAUNCH_CHECK();
-    } else {
-      rc = gemm_dispatch(emb, ids, d_item_emb, slab, m, sample_items, d, st);
-      if (rc) return rc;
-    }
-    if (d_r_indptr && !split) {
-      mask_kernel<<<(int)((m + 3) / 4), 256, 0, st>>>(ids, (int)m, d_r_indptr, d_r_indices, slab, (int)sample_items, (int)lo);
-      SRH_LAUNCH_CHECK();
-    }
-    if (split) {
-      // (the split path needs the bound only, not the sample's ranked list: one pass, one wave per row, the row's masks
-      // applied by the same wave)
-      bound_rows_kernel<<<(int)((m + 3) / 4), 256, 0, st>>>(slab, (int)m, (int)sample_items, k, s_sc + (k - 1), k, ids, (int)lo,
-                                                            d_r_indptr, d_r_indices, column_of_item);
-      SRH_LAUNCH_CHECK();
-    } else {
-      rc = srh_topk_rows(slab, m, sample_items, k, s_ids, s_sc, stream);
-      if (rc) return rc;
-    }
-    // 2. all scores again, never stored: only those reaching the bound and not masked are kept
-    hipError_t err = hipMemsetAsync(cnt, 0, sizeof(int32_t) * m, st);
-    if (err != hipSuccess) { srh::set_error("score_mask_topk_filtered: %s", hipGetErrorString(err)); return SRH_ERR_HIP; }
-    if (split) {
-      // 2'. the filter on split-bf16 operands against the bound lowered by its error margins ...
-      // 256 query rows per workgroup; the item tiles are dealt over enough workgroups to give every CU two
-      const int n_tiles = (int)((n_items + 31) / 32);
-      const int gy = (int)((m + 255) / 256);
-      const int gx = std::max(1, std::min(n_tiles, (512 + gy - 1) / gy));
-      const int tiles_per_wg = (n_tiles + gx - 1) / gx;
-      dim3 grid((unsigned)((n_tiles + tiles_per_wg - 1) / tiles_per_wg), (unsigned)gy);
-      Filter16Args f16{s_sc + (k - 1), k, u_norm, i_norm, order, cnt, cand_id, cand_sc, cap};
-      if (d == 64) filter16_kernel<64, false, SRH_F16_UB><<<grid, 512 / SRH_F16_UB, kF16Lds, st>>>(u_hi, u_lo, i_hi, (int)m, (int)n_items, f16);
-      else filter16_kernel<128, false, SRH_F16_UB><<<grid, 512 / SRH_F16_UB, kF16Lds, st>>>(u_hi, u_lo, i_hi, (int)m, (int)n_items, f16);
-      SRH_LAUNCH_CHECK();
-      // 3'. ... and the survivors re-scored by gemm_nt_kernel's own instruction sequence, masked, ranked
-      // (training-row membership by an LDS bitmap over the catalogue while it fits: <= 16 KB, i.e. 131 k items)
-      const int bitmap_words = (d_r_indptr && n_items <= 131072) ? (int)((n_items + 31) / 32) : 0;
-      const size_t rs_lds = (size_t)cap * 16 + (size_t)bitmap_words * 4;
-      // short lists (all but a few per cent of the rows) by a wave each, the rest by a workgroup each
-      constexpr int kWaveRows = 128;               // (longer lists: the O(n^2) rank counts want the 256 threads of the workgroup form)
-      const int wg = (int)((m + 3) / 4);
-      if (d == 64) {
-        rescore_wave_kernel<64, kWaveRows><<<wg, 256, 0, st>>>(emb, ids, (int)lo, d_item_emb, (int)m, cnt, cand_id, cand_sc, u_norm, norm_by_item,
-                                                               s_sc + (k - 1), k, cap, k, d_r_indptr, d_r_indices,
-                                                               d_out_ids + lo * k, d_out_scores + lo * k);
-        rescore_topk_kernel<64><<<(int)m, 256, rs_lds, st>>>(emb, ids, (int)lo, d_item_emb, cnt, cand_id, cand_sc, u_norm,
-                                                             norm_by_item, s_sc + (k - 1), k, cap, k, bitmap_words, d_r_indptr, d_r_indices,
-                                                             d_out_ids + lo * k, d_out_scores + lo * k, kWaveRows);
-      } else {
-        rescore_wave_kernel<128, kWaveRows><<<wg, 256, 0, st>>>(emb, ids, (int)lo, d_item_emb, (int)m, cnt, cand_id, cand_sc, u_norm, norm_by_item,
-                                                                s_sc + (k - 1), k, cap, k, d_r_indptr, d_r_indices,
-                                                                d_out_ids + lo * k, d_out_scores + lo * k);
-        rescore_topk_kernel<128><<<(int)m, 256, rs_lds, st>>>(emb, ids, (int)lo, d_item_emb, cnt, cand_id, cand_sc, u_norm,
-                                                              norm_by_item, s_sc + (k - 1), k, cap, k, bitmap_words, d_r_indptr, d_r_indices,
-                                                              d_out_ids + lo * k, d_out_scores + lo * k, kWaveRows);
-      }
-      SRH_LAUNCH_CHECK();
-      continue;
-    }
-    FilterArgs fa{s_sc + (k - 1), k, cnt, cand_id, cand_sc, cap};
-    rc = gemm_dispatch(emb, ids, d_item_emb, nullptr, m, n_items, d, st, &fa);
-    if (rc) return rc;
-    // 3. exact order of the survivors
-    cand_topk_kernel<<<(int)m, 256, (size_t)cap * 8, st>>>(cnt, cand_id, cand_sc, cap, k, ids, (int)lo, d_r_indptr, d_r_indices,
-                                                           d_out_ids + lo * k, d_out_scores + lo * k);
-    SRH_LAUNCH_CHECK();
-  }
-  return SRH_OK;
+  const FiltCall call{d_user_emb, d_user_ids, n_query, d_item_emb, n_items, d_r_indptr, d_r_indices, k, sample_items, cap, chunk_rows,
+                      reinterpret_cast<char*>(d_ws), d_out_ids, d_out_scores, d_out_counts, srh::as_stream(stream)};
+  const FiltLayout layout = filt_layout(chunk_rows, sample_items, k, cap, n_items, d);
+  if (d == 64) return filt_split_pipeline<64>(call, layout);
+  if (d == 128) return filt_split_pipeline<128>(call, layout);
+  return filt_f32_pipeline(call, layout, d);
 }
 
 srh_status_t srh_topk_hit_flags(const int32_t* d_ids, int64_t n_query, int32_t k, const int32_t* d_user_ids,

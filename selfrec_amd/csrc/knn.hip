@@ -56,14 +56,6 @@ __device__ __forceinline__ bool sc_before(double sa, int ia, double sb, int ib) 
   return sa > sb || (sa == sb && ia < ib);
 }
 
-__device__ __forceinline__ int lower_bound_i32(const int32_t* __restrict__ a, int lo, int hi, int x) {
-  while (lo < hi) {
-    const int mid = (lo + hi) >> 1;
-    if (a[mid] < x) lo = mid + 1; else hi = mid;
-  }
-  return lo;
-}
-
 __global__ __launch_bounds__(kNbThreads) void knn_neighbours_kernel(
     const int32_t* __restrict__ a_indptr, const int32_t* __restrict__ a_indices, const int32_t* __restrict__ t_indptr,
     const int32_t* __restrict__ t_indices, const double* __restrict__ norm, const int32_t* __restrict__ name_rank,
@@ -100,7 +92,7 @@ __global__ __launch_bounds__(kNbThreads) void knn_neighbours_kernel(
       const int f = a_indices[p];
       int lo = t_indptr[f];
       const int hi = t_indptr[f + 1];
-      if (c0 > 0) lo = lower_bound_i32(t_indices, lo, hi, c0);
+      if (c0 > 0) lo = srh::lower_bound_i32(t_indices, lo, hi, c0);
       for (int j = lo + lane; j < hi; j += 64) {
         const int v = t_indices[j];
         if (v >= c1) break;

@@ -353,3 +353,43 @@ def test_collective_entry_points_resolve_rccl_and_refuse_bad_arguments():
     assert lib.srh_reducescatter_rows(fake, fake, 0, 64, fake, None) == -1 and b"bad shape" in lib.srh_last_error_string()
     assert lib.srh_allreduce_sum_f32(None, 8, fake, None) == -1
     assert lib.srh_comm_destroy(None) == 0
+
+
+def _a256(x):
+    return (x + 255) // 256 * 256
+
+
+def _filtered_ws_f32(rows, sample, k, cap):
+    """The closed form include/selfrec_hip.h states for the widths the f32 pipeline serves."""
+    return _a256(4 * rows * sample) + 2 * _a256(4 * rows * k) + 2 * _a256(4 * rows * cap)
+
+
+def test_filtered_ranking_workspace_size_is_the_documented_closed_form():
+    """srh_score_mask_topk_filtered_ws_bytes answers on the host, without a device: 0 for a non-positive argument, a multiple
+    of 256, and for d = 32 / 256 the header's closed form -- one slab, two (rows, k) and two (rows, cap) arrays.  d = 64 / 128
+    adds the bf16 images, the norms and the norm order plus the radix sort's scratch, whose size the sort library decides:
+    bounded from below by the documented arrays and from above by what the layout took before it lost the lo images and the
+    unused per-row counter slot (3,787,776 / 36,925,440 / 113,054,208 bytes at these shapes)."""
+    ws = _lib.load().srh_score_mask_topk_filtered_ws_bytes
+    good = (300, 1000, 20, 64, 4133, 32)
+    for pos in range(6):
+        for bad in (0, -1):
+            args = list(good)
+            args[pos] = bad
+            assert ws(*args) == 0, args
+    assert _filtered_ws_f32(300, 1000, 20, 64) == 1401856 and _filtered_ws_f32(128, 1000, 128, 512) == 1167360
+    assert ws(300, 1000, 20, 64, 4133, 32) == 1401856
+    assert ws(128, 1000, 128, 512, 4133, 256) == 1167360
+    for rows, sample, k, cap, n_items in ((300, 1000, 20, 64, 4133), (1, 20, 20, 20, 20), (4096, 4096, 20, 1024, 38048)):
+        for d in (32, 256):
+            assert ws(rows, sample, k, cap, n_items, d) == _filtered_ws_f32(rows, sample, k, cap), (rows, sample, k, cap, d)
+    for (rows, sample, k, cap, n_items, d), parent in (((300, 1000, 20, 64, 4133, 128), 3787776),
+                                                       ((32, 1000, 20, 256, 131105, 64), 36925440),
+                                                       ((4096, 4096, 20, 1024, 38048, 64), 113054208)):
+        got = ws(rows, sample, k, cap, n_items, d)
+        padded = (n_items + 31) // 32 * 32
+        documented = _a256(2 * padded * d) + _a256(2 * rows * d) + _a256(4 * rows) + 6 * _a256(4 * padded)
+        print(f"ws_bytes{(rows, sample, k, cap, n_items, d)} = {got}: f32 part {_filtered_ws_f32(rows, sample, k, cap)}, "
+              f"images + norm order {documented}, sort scratch {got - _filtered_ws_f32(rows, sample, k, cap) - documented}; was {parent}")
+        assert got % 256 == 0
+        assert _filtered_ws_f32(rows, sample, k, cap) + documented <= got <= parent

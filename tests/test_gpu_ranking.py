@@ -235,15 +235,16 @@ def _expected_overflow(case, with_mask, split, K, cap, planted_room=False):
     return over, exact
 
 
-def _run_filtered(case, d, K, cap, chunk_rows, ids_kind, with_mask, planted_room=False):
+def _run_filtered(case, d, K, cap, chunk_rows, ids_kind, with_mask, planted_room=False, ws=None):
     split = d in (64, 128)
     over_u, exact_u = _expected_overflow(case, with_mask, split, K, cap, planted_room)
     users = case["perm"] if ids_kind == "shuffled" else np.arange(case["m"])
     indptr, indices = (case["indptr"], case["indices"]) if with_mask else (None, None)
-    ids, sc, counts, _ = ops.score_mask_topk_filtered(
+    ids, sc, counts, used_ws = ops.score_mask_topk_filtered(
         _dev(case["U"]), _dev(users) if ids_kind == "shuffled" else None, _dev(case["I"]),
         None if indptr is None else _dev(indptr), None if indices is None else _dev(indices), K,
-        sample_items=SAMPLE, cap=cap, chunk_rows=chunk_rows)
+        sample_items=SAMPLE, cap=cap, chunk_rows=chunk_rows, ws=ws)
+    assert ws is None or used_ws.data_ptr() == ws.data_ptr()                   # (the caller's workspace was large enough)
     counts = counts.cpu().numpy()
     what = f"d={d} K={K} cap={cap} chunk={chunk_rows} ids={ids_kind} mask={with_mask}"
     got_over = counts > cap
@@ -287,6 +288,25 @@ def test_filtered_ranking_against_the_host_ranking(d, K, cap):
         assert ((counts > 128) & (counts <= cap)).any()                        # complete long lists: a workgroup each
     if cap == 64:
         assert ((counts > cap) & (counts <= 128)).any()                        # overflowed AND short: nobody ranks them
+
+
+@pytest.mark.parametrize("d", [32, 64])
+def test_filtered_ranking_stays_inside_the_workspace_it_asked_for(d):
+    """The entry point carves its workspace by the layout srh_score_mask_topk_filtered_ws_bytes sizes: given exactly that
+    many bytes at the head of a larger allocation filled with 0xA5, it leaves the 4096 bytes behind them untouched and
+    ranks as ever (K = 20, cap = 64, chunks of 128 -- three of them, the last of 44 rows -- mask present, ids shuffled;
+    d = 32: the f32 pipeline, d = 64: the bf16 one).  The guard lies inside the allocation: a layout that disagrees
+    with its size fails here and faults nowhere."""
+    from selfrec_amd import _lib
+    case = _filtered_case(d)
+    K, cap, chunk_rows = 20, 64, 128
+    need = int(_lib.load().srh_score_mask_topk_filtered_ws_bytes(chunk_rows, SAMPLE, K, cap, case["I"].shape[0], d))
+    assert need > 0
+    buf = torch.full((need + 4096,), 0xA5, dtype=torch.uint8, device=DEV)
+    _run_filtered(case, d, K, cap, chunk_rows, "shuffled", True, ws=buf[:need])
+    torch.cuda.synchronize()
+    touched = int((buf[need:] != 0xA5).sum())
+    assert touched == 0, f"{touched} of the 4096 bytes behind the workspace's {need} were written"
 
 
 def test_filtered_ranking_large_catalogue_binary_search():
