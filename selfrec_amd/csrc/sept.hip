@@ -16,8 +16,10 @@
 //            exp(s_a - 1) / rs_a[i] + exp(s_b - 1) / rs_b[i], a top-k list per row kept in LDS -> pos and a membership
 //            bitmask of n bits per row.  The key of (i, j) is a function of rows i and j and of row i's two sums only,
 //            never of the tile, so identical aug rows tie exactly and the scan (ascending j, strict >) keeps the lower j.
-//   rowgrad  per view and row tile: O1_i = sum_j e_ij a_j, O2_i = sum_{j in pos} e_ij a_j and sum_{j in pos} e_ij in one
-//            sweep (two-MFMA form of contrastive.hip); dL/dv_i = g (O1_i / sum_j e - O2_i / sum_pos e), g = scale / tau,
+//   rowgrad  per view and row tile: Oout_i = sum_{j not in pos} e_ij a_j, Opos_i = sum_{j in pos} e_ij a_j and
+//            sum_{j in pos} e_ij in one sweep (two-MFMA form of contrastive.hip); with g = scale / tau,
+//            dL/dv_i = g ((Oout_i + Opos_i) / sum_j e - Opos_i / sum_pos e), taken as
+//            g (Oout_i / sum_j e - Opos_i (sum_j e - sum_pos e) / (sum_j e sum_pos e)) with the factor in double;
 //            then the normalisation backward; the row's loss term and its two key-side weights
 //   keygrad  key tiles x (3 views x all rows): dL/da_j = g sum_v sum_i e_ij (1 / sum_j e - [j in pos_v[i]] / sum_pos e) v_i,
 //            each key tile owns its rows of dL/dA; then the normalisation backward
@@ -409,10 +411,10 @@ __global__ __launch_bounds__(256) void tn_rowgrad(TnArgs a) {
       for (int reg = 0; reg < 4; ++reg) {
         const bool cok = c0 + sub * 16 + 4 * g + reg < n;
         const float e = cok ? expf((s[reg] - 1.f) * inv_tau) : 0.f;
-        const float em = ((mw >> reg) & 1u) ? e : 0.f;
-        sp += (double)em;
-        s[reg] = e;
-        sm[reg] = em;
+        const bool in = (mw >> reg) & 1u;
+        sp += (double)(in ? e : 0.f);
+        s[reg] = in ? 0.f : e;   // o1: the keys off the list; o2: the positives
+        sm[reg] = in ? e : 0.f;
       }
 #pragma unroll
       for (int b = 0; b < D / 16; ++b) {
@@ -430,14 +432,17 @@ __global__ __launch_bounds__(256) void tn_rowgrad(TnArgs a) {
   sp += __shfl_xor(sp, 32);
   const int64_t e = (int64_t)v * n + (rok ? r : 0);
   const double rsT = rok ? a.rsT[e] : 1.0;
-  const float cw = (float)(1.0 / rsT), cp = rok ? (float)(1.0 / sp) : 0.f;
+  const float cw = (float)(1.0 / rsT);
+  // (Oout + Opos) / sum_j e - Opos / sum_pos e = Oout / sum_j e - Opos (sum_j e - sum_pos e) / (sum_j e sum_pos e): where
+  // the positives hold nearly all of the sum both terms are small, and the two large ones never meet in float32
+  const float cd = rok ? (float)((rsT - sp) / (rsT * sp)) : 0.f;
   const float gs = a.gscale;
 #pragma unroll
   for (int b = 0; b < D / 16; ++b)
 #pragma unroll
-    for (int reg = 0; reg < 4; ++reg) o1[b][reg] = gs * (o1[b][reg] * cw - o2[b][reg] * cp);
+    for (int reg = 0; reg < 4; ++reg) o1[b][reg] = gs * (o1[b][reg] * cw - o2[b][reg] * cd);
   if (rok && g == 0) {
-    a.cp[e] = cp;
+    a.cp[e] = (float)(1.0 / sp);
     a.row_loss[e] = log(rsT) - log(sp);
   }
   norm_bwd_store<D>(o1, a.vn[v], rok ? a.vinv[v][r] : 1.f, r, rok, g, a.gv[v]);

@@ -4,6 +4,8 @@ losses) and util/loss_tf.py bpr_loss, with the gradients derived by hand (the TF
 tests/test_sept_cpu.py holds them to torch.autograd on the literal expression."""
 import numpy as np
 
+from tests import contrastive_ref
+
 EPS = 1e-12                       # tf.nn.l2_normalize's epsilon, on the squared norm
 PAIRS = ((1, 2), (0, 2), (0, 1))  # SEPT.py:145-147: friend <- (sharing, rec), sharing <- (friend, rec), rec <- (friend, sharing)
 
@@ -64,6 +66,51 @@ def tri_nd(F, S, R, A, k, tau=0.1, loss_scale=1.0, pos=None):
 
 def ambiguous(gap, bound=1e-4):
     return gap < bound
+
+
+def row_errors(got, want, floor_frac=0.0):
+    """contrastive_ref.row_errors as a float64 numpy (n,): per row max|got - want| / max(max|want_row|, floor_frac *
+    max|want|); no floor unless one is asked for"""
+    return contrastive_ref.row_errors(np.asarray(got, dtype=np.float64), np.asarray(want, dtype=np.float64),
+                                      floor_frac).numpy()
+
+
+def tri_nd_f32(F, S, R, A, k, tau, pos):
+    """tri_nd's own expression at the given ids in plain float32 numpy -- a YARDSTICK, not a second reference: how far
+    float32 arithmetic alone moves each loss and each gradient row of an input.  Normalise, exp((s - 1) / tau), the two
+    sums, ds, the two products, the normalisation backward; every array float32, numpy's own summation order.
+    -> dict: loss (3, float32), grads (dF, dS, dR, dA float32)"""
+    f32 = np.float32
+    one, eps, inv_tau = f32(1.0), f32(EPS), f32(1.0) / f32(tau)
+
+    def norm(x):
+        x = np.asarray(x, dtype=f32)
+        ss = (x * x).sum(1, dtype=f32)
+        clamped = ss < eps
+        inv = np.where(clamped, f32(1e6), one / np.sqrt(np.maximum(ss, eps))).astype(f32)
+        return x * inv[:, None], inv, clamped
+
+    def norm_bwd(g, out, inv, clamped):
+        proj = (g - out * (out * g).sum(1, keepdims=True, dtype=f32)) * inv[:, None]
+        return np.where(clamped[:, None], g * inv[:, None], proj).astype(f32)
+
+    an, ainv, aclamp = norm(A)
+    n = an.shape[0]
+    pos = np.asarray(pos).astype(np.int64)
+    loss, grads, gan = np.zeros(3, dtype=f32), [], np.zeros_like(an)
+    for v, V in enumerate((F, S, R)):
+        vn, vinv, vclamp = norm(V)
+        e = np.exp((vn @ an.T - one) * inv_tau)
+        member = np.zeros((n, n), dtype=f32)
+        np.put_along_axis(member, pos[v], one, axis=1)
+        ttl, ps = e.sum(1, dtype=f32), (e * member).sum(1, dtype=f32)
+        loss[v] = -np.log(ps / ttl).sum(dtype=f32)
+        ds = inv_tau * (e / ttl[:, None] - member * e / ps[:, None])
+        grads.append(norm_bwd(ds @ an, vn, vinv, vclamp))
+        gan += ds.T @ vn
+    grads.append(norm_bwd(gan, an, ainv, aclamp))
+    assert all(g.dtype == f32 for g in grads)
+    return dict(loss=loss, grads=grads)
 
 
 def encoder(emb, adj, n_layers):

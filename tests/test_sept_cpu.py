@@ -1,6 +1,7 @@
 """SEPT without a GPU: the social data path against the reference's own run (tests/golden/sept.npz, sept_mats.npz), the
-float64 restatement tests/sept_ref.py against torch.autograd on the literal expression, how many top-k cuts of the GPU
-cases float32 cannot call, and the housekeeping around the new entry points."""
+float64 restatement tests/sept_ref.py against torch.autograd on the literal expression (clamped rows included), how many
+top-k cuts of the GPU cases float32 cannot call, what plain float32 loses on the edge cases (the yardstick of
+tests/test_gpu_sept_edges.py), and the housekeeping around the new entry points."""
 import json
 import os
 import re
@@ -251,6 +252,96 @@ def test_gpu_cases_are_mostly_unambiguous(case):
     assert share <= sept_cases.AMBIGUOUS_SHARE
     if clean:
         assert not c["amb"].any()
+
+
+@pytest.mark.parametrize("case", sept_cases.edge_cases(), ids=sept_cases.edge_id)
+def test_edge_cases_are_mostly_unambiguous(case):
+    """every (shape, family) of the edge suite keeps the same 5 % cap -- a condition on the cases, measured on the
+    restatement alone.  `clamped`: the planted rows, and no others, are below the clamp, far from it on either side, and
+    the cap holds without them too (they are checked on their own on the device, not through the allowance)."""
+    (n, d, k, seed), fam = case
+    c = sept_cases.edge_case(*case)
+    share = float(c["amb"].mean())
+    print(f"{sept_cases.edge_id(case)}: ambiguous share {share:.4f}, smallest gap {float(c['ref']['gap'].min()):.3e}")
+    assert share <= sept_cases.AMBIGUOUS_SHARE
+    norms = [np.sqrt((m.astype(np.float64) ** 2).sum(1)) for m in c["mats"]]
+    if fam != "clamped":
+        assert min(float(x.min()) for x in norms) > 1e-3
+        return
+    planted = sept_cases.planted_rows(n)
+    assert len({r for pair in planted for r in pair}) == 8
+    for m, x, (zero, tiny) in zip(c["mats"], norms, planted):
+        clamped = sept_ref.l2norm(m)[2]
+        assert sorted(np.flatnonzero(clamped).tolist()) == sorted((zero, tiny))
+        # 1e-8 * standard_normal(d): a norm of about 1e-8 sqrt(d), at most a quarter of the clamp's 1e-6 at d = 128
+        assert x[zero] == 0.0 and 0.0 < x[tiny] < 2.5e-7
+        assert float(np.delete(x, (zero, tiny)).min()) > 1e-3
+    rest = np.setdiff1d(np.arange(n), [r for pair in planted[:3] for r in pair])
+    assert float(c["amb"][:, rest].mean()) <= sept_cases.AMBIGUOUS_SHARE
+
+
+def test_padded_width_seeds_are_the_smallest_that_meet_the_cap():
+    """the two zero-padded shapes carry a literal seed: the smallest of 0 ... 9 at which all four families meet the cap"""
+    for shape in sept_cases.EDGE_SHAPES:
+        n, d, k, seed = shape
+        if d not in (100, 8):
+            continue
+        ok = [s for s in range(10)
+              if all(float(sept_cases.edge_case((n, d, k, s), f)["amb"].mean()) <= sept_cases.AMBIGUOUS_SHARE
+                     for f in sept_cases.FAMILIES)]
+        assert ok and ok[0] == seed, (shape, ok)
+    assert {s[1] for s in sept_cases.EDGE_SHAPES} >= {100, 8}
+
+
+def test_tri_nd_restatement_against_autograd_with_clamped_rows():
+    """the clamped branches of the restatement (a zero row and a row below the clamp in each view and in aug) against
+    autograd on x * rsqrt(maximum(sum x^2, 1e-12)): n = 33, d = 8, k = 10, to the same 1e-10 -- absolute on ordinary
+    rows, relative to the row's own 1e6-scaled entries on the planted ones"""
+    n, d, k = 33, 8, 10
+    mats = sept_cases.family("clamped", n, d, 3)
+    planted = sept_cases.planted_rows(n)
+    leaves = [torch.from_numpy(m).double().requires_grad_(True) for m in mats]
+    losses, pos = t_tri_nd(*leaves, k, sept_cases.TAU)
+    (0.37 * sum(losses)).backward()
+    ref = sept_ref.tri_nd(*mats, k, sept_cases.TAU, loss_scale=0.37)
+    assert np.array_equal(ref["pos"], pos.numpy())
+    for v in range(3):
+        assert abs(ref["loss"][v] - 0.37 * losses[v].item()) <= 1e-10
+    for g, leaf, m, rows in zip(ref["grads"], leaves, mats, planted):
+        clamped = sept_ref.l2norm(m)[2]
+        assert sorted(np.flatnonzero(clamped).tolist()) == sorted(rows)
+        want = leaf.grad.numpy()
+        assert np.abs(g - want)[~clamped].max() <= 1e-10
+        assert sept_ref.row_errors(g, want).max() <= 1e-10
+        assert np.abs(want[clamped]).max(1).min() > 1e3          # the planted rows carry g * 1e6, not a projection
+
+
+# ---- the float32 yardstick of the edge suite ------------------------------------------------------------------------------
+YARDSTICK_ROW, YARDSTICK_LOSS = 5e-6, 1e-6
+
+
+@pytest.mark.parametrize("fam", sept_cases.FAMILIES)
+def test_f32_yardstick_against_the_restatement(fam):
+    """sept_ref.tri_nd_f32 against sept_ref.tri_nd at the restatement's ids, per row with no floor, on every shape: what
+    float32 arithmetic alone does to these inputs, and so what the device bounds rest on.  normal / scaled / clamped
+    (the planted rows relative to their own 1e6-scaled entries): <= 5e-6 per row, twice the largest value measured
+    (2.4e-6), 20x below GRAD_BOUND; the loss <= 1e-6 (1.5e-7 measured), 10x below LOSS_BOUND.  peaked: the loss and the
+    row gradients are small differences of large terms (2.1e-4 and 1.1e-5 at the worst), so the device bound is taken
+    per case from this yardstick; here only finite and below 1e-3."""
+    worst_row, worst_loss = 0.0, 0.0
+    for shape in sept_cases.EDGE_SHAPES:
+        c = sept_cases.edge_case(shape, fam)
+        y = sept_ref.tri_nd_f32(*c["mats"], shape[2], sept_cases.TAU, c["ref"]["pos"])
+        row = max(float(sept_ref.row_errors(g, w).max()) for g, w in zip(y["grads"], c["ref"]["grads"]))
+        loss = float(np.abs(y["loss"].astype(np.float64) / c["ref"]["loss"] - 1).max())
+        print(f"{sept_cases.edge_id((shape, fam))}: yardstick row {row:.3e} loss {loss:.3e}")
+        assert np.isfinite(row) and np.isfinite(loss)
+        if fam == "peaked":
+            assert row < 1e-3 and loss < 1e-3
+        else:
+            assert row <= YARDSTICK_ROW and loss <= YARDSTICK_LOSS
+        worst_row, worst_loss = max(worst_row, row), max(worst_loss, loss)
+    print(f"{fam}: largest yardstick row error {worst_row:.3e}, loss error {worst_loss:.3e}")
 
 
 # ---- housekeeping -----------------------------------------------------------------------------------------------------------
