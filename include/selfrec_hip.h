@@ -438,6 +438,12 @@ srh_status_t srh_infonce_fwd_bwd_multi(const srh_infonce_problem_t* problems, in
 srh_status_t srh_infonce_set_precision(int32_t mode);
 int32_t srh_infonce_get_precision(void);
 
+/* How the SRH_NCE_F32 passes cut `count` (1..4) problems of n[k] live rows into tasks on `slots` persistent workgroups (one
+ * per compute unit in a call).  HOST ONLY: launches nothing, needs no device.  out17 receives the record the passes read,
+ * 17 int32: n[4], per[4] (32-key blocks per task), splits[4] (key ranges per 128-row query block), first[5] (running task
+ * count; first[4] = tasks in all).  per <= 128 and splits <= 16 for every n <= 65536; larger n: SRH_ERR_UNSUPPORTED. */
+srh_status_t srh_infonce_plan(const int32_t* n, int32_t count, int32_t slots, int32_t* out17);
+
 /* The whole batch objective of XSimGCL.py:30-35 / SimGCL.py:33-36 / SGL.py:33-37 --
  *   rec_loss + l2_reg_loss + cl_rate * cl_loss  and its gradients w.r.t. the gathered tables --
  * in one call: exactly srh_bpr_l2_fwd_bwd(bpr...) followed by srh_infonce_fwd_bwd_multi(problems...),

@@ -174,6 +174,7 @@ SIGNATURES = {
     "srh_infonce_ws_bytes": (_i64, [_i64, _i32]),
     "srh_infonce_set_precision": (_i32, [_i32]),
     "srh_infonce_get_precision": (_i32, []),
+    "srh_infonce_plan": (_i32, [_vp, _i32, _i32, _vp]),
     "srh_infonce_fwd_bwd": (_i32, [_vp, _vp, _vp, _i64, _vp, _i32, _f32, _f32, _vp, _vp, _vp, _vp, _vp]),
     "srh_infonce_fwd_bwd_multi": (_i32, [C.POINTER(InfonceProblem), _i32, _i32, _f32, _f32, _vp, _vp, _i32, _vp]),
     "srh_bpr_infonce_fwd_bwd": (_i32, [C.POINTER(BprProblem), C.POINTER(InfonceProblem), _i32, _i32, _f32, _f32, _vp, _vp,

@@ -6,6 +6,7 @@
 // (v_mfma_f32_16x16x4_f32: exact f32 fma chains, so the 1e-4 parity budget is untouched).
 #include <atomic>
 #include <cstdlib>
+#include <cstring>
 #include <type_traits>
 
 #include "common.h"
@@ -377,29 +378,35 @@ constexpr int kNceQueryBlock = 128, kNceKeyBlock = 32, kNceMaxPer = 128;
 constexpr int kNceReuseMax = 8192;      // pass 1 keeps its n x n weights for pass 2 up to this n (256 MB per problem)
 
 
-__device__ __forceinline__ void nce_plan(const NceBatch& b, NcePlan& p) {
+// The cut from the live counts n[0 .. kNceMaxProblems) (0: no such problem) on `slots` workgroups.  Host and device: the
+// passes' prep kernel runs it once per step, srh_infonce_plan answers the same question without a launch.
+// A task's 1 / l values sit in kNceMaxPer x 32 floats of LDS (NceF32::kLds), so the block budget never exceeds kNceMaxPer:
+// with n <= 65 536 (launch_infonce refuses more) t_min <= kNceMaxPer and a cut exists; what the budget leaves over
+// becomes more tasks than workgroups, which the passes' task loop strides over.
+__host__ __device__ inline void nce_plan(const int* n_live, int slots, NcePlan& p) {
   int qb[kNceMaxProblems], kb[kNceMaxProblems];
   int t_min = 1;
   long long work = 0;
 #pragma unroll
   for (int k = 0; k < kNceMaxProblems; ++k) {
-    int n = 0;
-    if (k < b.count) n = max(0, b.w[k].d_n ? min(*b.w[k].d_n, b.w[k].n_max) : b.w[k].n_max);
+    const int n = n_live[k];
     p.n[k] = n;
     const int np = (int)nce_pad(n);
     qb[k] = (np + kNceQueryBlock - 1) / kNceQueryBlock;
     kb[k] = np / kNceKeyBlock;
-    t_min = max(t_min, (kb[k] + kNceSplits - 1) / kNceSplits);
+    const int need = (kb[k] + kNceSplits - 1) / kNceSplits;
+    t_min = t_min > need ? t_min : need;
     work += (long long)qb[k] * kb[k];
   }
-  int t = max(t_min, (int)((work + b.slots - 1) / b.slots));
+  const long long even = (work + slots - 1) / slots;
+  int t = even > t_min ? (even < kNceMaxPer ? (int)even : kNceMaxPer) : t_min;
   int best_t = t;
   long long best_cost = -1;
-  for (int it = 0; it < 32; ++it, ++t) {
+  for (int it = 0; it < 32 && (t <= kNceMaxPer || it == 0); ++it, ++t) {
     int tasks = 0;
 #pragma unroll
     for (int k = 0; k < kNceMaxProblems; ++k) tasks += qb[k] * ((kb[k] + t - 1) / t);
-    const int rounds = (tasks + b.slots - 1) / b.slots;
+    const int rounds = (tasks + slots - 1) / slots;
     const long long cost = (long long)rounds * t;
     if (best_cost < 0 || cost < best_cost) { best_cost = cost; best_t = t; }
     if (rounds <= 1) break;
@@ -469,7 +476,13 @@ __device__ __forceinline__ void nce_prep_body(const NceBatch& batch, const unsig
   // the kernel; tools/nce_stamps.py)
   if (batch.slots > 0 && bx == 0 && by == 0 && bz == 0 && threadIdx.x == 0) {
     NcePlan plan;
-    nce_plan(batch, plan);
+    int n_live[kNceMaxProblems];
+#pragma unroll
+    for (int k = 0; k < kNceMaxProblems; ++k) {
+      n_live[k] = 0;
+      if (k < batch.count) n_live[k] = max(0, batch.w[k].d_n ? min(*batch.w[k].d_n, batch.w[k].n_max) : batch.w[k].n_max);
+    }
+    nce_plan(n_live, batch.slots, plan);
     *batch.w[0].plan = plan;
   }
   const float* V = second ? V2 : V1;
@@ -1333,7 +1346,8 @@ __global__ __launch_bounds__(512) void nce_tile_f32(NceBatch batch, float inv_ta
 // One finish for both passes (used with nce_tile_lds): folds the split partials, turns them into the
 // gradients of both views (through the normalisation) and scatters them; the loss partials are folded
 // in workgroup order by whichever workgroup of the problem arrives last (write-through partial ->
-// vmcnt(0) -> relaxed agent-scope ticket -> acquire), so the reported loss is bitwise reproducible.
+// vmcnt(0) -> relaxed agent-scope ticket -> acquire), and the problems' terms in problem order by whichever problem
+// finishes last, so the reported loss is bitwise reproducible.
 template <int LPR>
 __device__ __forceinline__ void nce_finish_both_body(const NceBatch& batch, const NceFinishArgs& a, const unsigned bx,
                                                      const unsigned bz) {
@@ -1367,7 +1381,34 @@ __device__ __forceinline__ void nce_finish_both_body(const NceBatch& batch, cons
       double t = 0.0;
       for (int k = lane; k < n_wgs; k += 64) t += w.losspart[k];
       t = wave_sum_d(t);
-      if (lane == 0) atomicAdd(a.loss, (double)a.loss_scale * t / (double)n);   // one per problem
+      const double mine = (double)a.loss_scale * t / (double)n;
+      if (batch.count == 1) {
+        if (lane == 0) atomicAdd(a.loss, mine);
+      } else {
+        // Several problems: one add per problem in arrival order gives other bits from run to run as soon as three terms
+        // meet (or two and a non-zero *loss).  Each problem leaves its term in the last slot of its losspart array (no
+        // workgroup's: n_wgs <= np / 4) and draws a second, call-wide ticket (problem 0's counter 1); the problem that
+        // finishes last adds the terms in problem order, once.  Problems of no rows never arrive and are not counted.
+        if (lane == 0) store_f64_sc1(w.losspart + w.np - 1, mine);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        int live = 0;
+        for (int k = 0; k < batch.count; ++k)
+          live += (batch.w[k].d_n ? min(*batch.w[k].d_n, batch.w[k].n_max) : batch.w[k].n_max) > 0;
+        int seen = 0;
+        if (lane == 0) seen = __hip_atomic_fetch_add(batch.w[0].ticket + 1, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        seen = __builtin_amdgcn_readfirstlane(seen);
+        if (seen == live - 1) {
+          __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+          if (lane == 0) {
+            __hip_atomic_store(batch.w[0].ticket + 1, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            double sum = 0.0;
+            for (int k = 0; k < batch.count; ++k)
+              if ((batch.w[k].d_n ? min(*batch.w[k].d_n, batch.w[k].n_max) : batch.w[k].n_max) > 0)
+                sum += batch.w[k].losspart[batch.w[k].np - 1];
+            atomicAdd(a.loss, sum);
+          }
+        }
+      }
     }
   }
 }
@@ -1884,6 +1925,26 @@ int64_t srh_infonce_ws_bytes(int64_t n, int32_t d) {
   return 4 * (2 * np * d + 2 * (int64_t)kNceSplits * np * d + 4 * np + (int64_t)kNceSplits * np) + 8 * np +
          20 * np * d + 4 * (np / 16) + 512 +      // (2 views x 5 sixteen-bit operand images; counters; the plan record)
          (np <= kNceReuseMax ? 4 * np * np : 0);  // (pass 1's weights for pass 2: NceWs::etile)
+}
+
+srh_status_t srh_infonce_plan(const int32_t* n, int32_t count, int32_t slots, int32_t* out17) {
+  SRH_REQUIRE(n && out17, "infonce_plan: null argument");
+  SRH_REQUIRE(count >= 1 && count <= kNceMaxProblems, "infonce_plan: 1..%d problems", kNceMaxProblems);
+  SRH_REQUIRE(slots >= 1, "infonce_plan: slots must be positive");
+  int n_live[kNceMaxProblems] = {0, 0, 0, 0};
+  for (int k = 0; k < count; ++k) {
+    SRH_REQUIRE(n[k] >= 0, "infonce_plan: negative n in problem %d", k);
+    if (nce_pad(n[k]) / kNceKeyBlock > (int64_t)kNceSplits * kNceMaxPer) {
+      srh::set_error("infonce_plan: the all-f32 MFMA path serves n <= %d", kNceSplits * kNceMaxPer * kNceKeyBlock);
+      return SRH_ERR_UNSUPPORTED;
+    }
+    n_live[k] = n[k];
+  }
+  NcePlan p;
+  nce_plan(n_live, slots, p);
+  static_assert(sizeof(NcePlan) == 17 * sizeof(int32_t), "srh_infonce_plan writes the NcePlan record: 17 int32");
+  memcpy(out17, &p, sizeof(p));
+  return SRH_OK;
 }
 
 static srh_status_t infonce_entry(const srh_infonce_problem_t* problems, int32_t n_problems, int32_t d, float tau,

@@ -731,6 +731,22 @@ def get_infonce_precision() -> str:
     return {0: "split", 1: "f32"}[got]
 
 
+NCE_F32_MAX_N = 65536          # the all-f32 passes: 16 key ranges of at most 128 blocks of 32 keys
+
+
+def infonce_plan(ns, slots: int) -> dict:
+    """The task cut of the all-f32 passes for problems of ns live rows on `slots` workgroups (srh_infonce_plan: host only,
+    nothing is launched): dict(n, per, splits: one entry per problem; first: len(ns) + 1 running task counts; tasks)."""
+    ns = [int(n) for n in ns]
+    arr = (C.c_int32 * max(len(ns), 1))(*ns)
+    out = (C.c_int32 * 17)()
+    check(_lib.load().srh_infonce_plan(C.cast(arr, C.c_void_p), len(ns), int(slots), C.cast(out, C.c_void_p)),
+          "srh_infonce_plan")
+    k = len(ns)
+    return dict(n=list(out[0:k]), per=list(out[4:4 + k]), splits=list(out[8:8 + k]), first=list(out[12:13 + k]),
+                tasks=int(out[16]))
+
+
 def infonce_ws(n: int, d: int, device):
     return torch.empty(int(_lib.load().srh_infonce_ws_bytes(n, d)), dtype=torch.uint8, device=device)
 
