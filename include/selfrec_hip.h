@@ -937,7 +937,12 @@ srh_status_t srh_seq_bce_fwd_bwd(const float* d_hidden, int64_t R, int32_t d, co
  *   all three WRITTEN.  The M x N logits and probabilities never reach memory; the softmax is max-subtracted (safe for
  *   any finite logits); no float atomics: one producer and one summation order per output element, the same bits on
  *   every call.  d = 64 or 128 (the caller zero-pads narrower rows), else SRH_ERR_UNSUPPORTED with a message; any M >= 1,
- *   N >= 1.  A label outside [0, N) reads nothing and makes the loss NaN.  d_ws >= srh_table_ce_ws_bytes(M, N, d).
+ *   N >= 1.  A label outside [0, N) reads nothing and makes the loss NaN; its row has no one-hot: d_gh of that row is
+ *   loss_scale * sum_j P_mj t_j, it takes nothing off any row of d_gt, and every other row of d_gh and all of d_gt are
+ *   what they are without it.  d_ws >= srh_table_ce_ws_bytes(M, N, d) and may hold anything on entry: every part of it
+ *   that is read was written by the same call first.  loss_scale is applied once, as the last float32 multiplication
+ *   of each gradient element and the last float64 one of the loss: 0 gives exact zeros, -1 the negated bits.  A
+ *   non-finite loss_scale or M, N outside [1, 2^31) is refused (SRH_ERR_INVALID_ARG) before any launch.
  *   F.cross_entropy(h @ t.T, labels) / M (BERT4Rec.py:61) is loss_scale = 1 / M^2.
  * ---------------------------------------------------------------------------------- */
 srh_status_t srh_seq_attn_full_fwd_f32(const float* d_q, const float* d_k, const float* d_v, int64_t B, int32_t L,

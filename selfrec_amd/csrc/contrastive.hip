@@ -37,7 +37,8 @@
 // temperature, so they have no bound and the softmax is max-subtracted.  Pass 1 keeps a running max per row, rescales its
 // sums when a key tile raises it (e = exp(s - max)) and writes (max, sum e, sum e T_j) per key chunk; the finish takes the
 // row's largest chunk max, merges the partials in chunk order with exp(max_c - max), and fixes lse_m; pass 2 weighs with
-// exp(s - lse_m) - [j == label_m] <= 1.  No prep launch: the rows are used as they are.
+// exp(s - lse_m) - [j == label_m] <= 1 and sums each 64-row tile from zero before adding it to the key's total (DESIGN.md
+// 4.20).  No prep launch: the rows are used as they are.
 #include <algorithm>
 #include <cmath>
 
@@ -455,6 +456,13 @@ __global__ __launch_bounds__(256) void ce_pass(CeArgs P) {
   f32x4 o[D / 16];
 #pragma unroll
   for (int b = 0; b < D / 16; ++b) o[b] = f32x4{0.f, 0.f, 0.f, 0.f};
+  // pass 2 sums every 64-row tile from zero and adds the tile's sum here: a key that many rows name builds up a sum of
+  // -H_m thousands of times the size of the P_mj H_m terms of all other rows, which a single running sum would then drop
+  f32x4 tot[PASS2 ? D / 16 : 1];
+  if (PASS2) {
+#pragma unroll
+    for (int b = 0; b < D / 16; ++b) tot[b] = f32x4{0.f, 0.f, 0.f, 0.f};
+  }
   double rs = 0.0;
   float m = -INFINITY;
 
@@ -524,6 +532,17 @@ __global__ __launch_bounds__(256) void ce_pass(CeArgs P) {
         for (int reg = 0; reg < 4; ++reg)
           o[b] = __builtin_amdgcn_mfma_f32_16x16x4f32(cs[(sub * 16 + 4 * g + reg) * LDS_STRIDE + 16 * b + j16], s[sub][reg],
                                                       o[b], 0, 0, 0);
+    if (PASS2) {
+#pragma unroll
+      for (int b = 0; b < D / 16; ++b) {
+        tot[b] += o[b];
+        o[b] = f32x4{0.f, 0.f, 0.f, 0.f};
+      }
+    }
+  }
+  if (PASS2) {
+#pragma unroll
+    for (int b = 0; b < D / 16; ++b) o[b] = tot[b];
   }
   // o[b][reg] = O[r][16b + 4g + reg]
   if (!PASS2) {
