@@ -482,6 +482,13 @@ srh_status_t srh_bpr_l2_fwd_bwd_p(const srh_bpr_problem_t* bpr, int32_t d, void*
 srh_status_t srh_bpr_infonce_fwd_bwd(const srh_bpr_problem_t* bpr, const srh_infonce_problem_t* problems,
                                      int32_t n_problems, int32_t d, float tau, float cl_scale,
                                      double* d_cl_loss, void* d_nce_ws, int32_t precision, void* stream);
+/* The same call for a step whose views were staged by the caller's product (srh_spmm_f32_with_nce_stage on the same
+ * problems, d and d_nce_ws, earlier on the stream): one launch fewer.  All-f32 arithmetic (SRH_NCE_F32), d = 64 / 128.  The
+ * first InfoNCE pass gathers and normalises its own query rows (the same bits the prep kernel stores) and carries the BPR
+ * scores at the end of its grid; losses and gradients are bit for bit those of srh_bpr_infonce_fwd_bwd at SRH_NCE_F32. */
+srh_status_t srh_bpr_infonce_fwd_bwd_staged(const srh_bpr_problem_t* bpr, const srh_infonce_problem_t* problems,
+                                            int32_t n_problems, int32_t d, float tau, float cl_scale,
+                                            double* d_cl_loss, void* d_nce_ws, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * (a-9) Dense Adam -- replaces torch.optim.Adam(...).step() at XSimGCL.py:25,37
@@ -638,6 +645,18 @@ srh_status_t srh_batch_fetch(const srh_batch_fetch_args_t* args, void* stream);
 srh_status_t srh_spmm_f32_with_fetch(const srh_spmm_plan_t* plan, const int32_t* d_indptr, const int32_t* d_indices,
                                      const float* d_vals, const float* d_x, float* d_y, int32_t d,
                                      const srh_spmm_epilogue_t* epi, const srh_batch_fetch_args_t* fetch, void* stream);
+/* srh_spmm_f32 for d = 64 / 128 whose launch ALSO stages what the all-f32 InfoNCE passes of `problems` need before their
+ * first launch and that depends on nothing later than the key-side tables d_v2: the gathered, normalised key-side view and
+ * its norms, the armed arrival counters and loss-partial slots, and the step's task plan (cut from the live counts *d_n) --
+ * rider workgroups (a multiple of 8) at the head of the launch, in d_nce_ws as srh_bpr_infonce_fwd_bwd lays it out.
+ * problems / n_problems / d / d_nce_ws: exactly what the step later hands to srh_bpr_infonce_fwd_bwd_staged (d_v1, d_g1 and
+ * d_g2 are not touched here).  The product must not write a d_v2 table (reading one is fine: the riders only read it), the
+ * batch's d_idx / d_n must be staged by an EARLIER launch, and nothing between this launch and the staged loss call may
+ * write d_nce_ws.  Not on an SRH_EPI_ADAM launch. */
+srh_status_t srh_spmm_f32_with_nce_stage(const srh_spmm_plan_t* plan, const int32_t* d_indptr, const int32_t* d_indices,
+                                         const float* d_vals, const float* d_x, float* d_y, int32_t d,
+                                         const srh_spmm_epilogue_t* epi, const srh_infonce_problem_t* problems,
+                                         int32_t n_problems, void* d_nce_ws, void* stream);
 
 /* srh_spmm_f32 (no column marks, d = 64 / 128 / 256) that also leaves, for task k of the list, d_stamps[3k .. 3k+2] =
  * {begin, end} of its wave on the chip-wide 100 MHz clock and the XCD (0 .. 7) it ran on; records of tasks that do not

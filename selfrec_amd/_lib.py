@@ -179,6 +179,8 @@ SIGNATURES = {
     "srh_infonce_fwd_bwd_multi": (_i32, [C.POINTER(InfonceProblem), _i32, _i32, _f32, _f32, _vp, _vp, _i32, _vp]),
     "srh_bpr_infonce_fwd_bwd": (_i32, [C.POINTER(BprProblem), C.POINTER(InfonceProblem), _i32, _i32, _f32, _f32, _vp, _vp,
                                        _i32, _vp]),
+    "srh_bpr_infonce_fwd_bwd_staged": (_i32, [C.POINTER(BprProblem), C.POINTER(InfonceProblem), _i32, _i32, _f32, _f32, _vp,
+                                              _vp, _vp]),
     "srh_table_nce_ws_bytes": (_i64, [_i64, _i64, _i32]),
     "srh_table_nce_fwd_bwd": (_i32, [C.POINTER(TableNceProblem), _i32, _i32, _f32, _vp, _vp]),
     "srh_kmeans_assign_f32": (_i32, [_vp, _i64, _vp, _i64, _i32, _vp, _vp, _vp]),
@@ -226,6 +228,8 @@ SIGNATURES = {
     "srh_axpby": (_i32, [_f32, _vp, _f32, _vp, _i64, _vp]),
     "srh_batch_fetch": (_i32, [_vp, _vp]),
     "srh_spmm_f32_with_fetch": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp]),
+    "srh_spmm_f32_with_nce_stage": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, C.POINTER(InfonceProblem), _i32, _vp,
+                                           _vp]),
     "srh_zero_rows": (_i32, [_i32, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp]),
     "srh_cursor_advance": (_i32, [_vp, _vp]),
     "srh_batch_pack": (_i32, [_vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp]),

@@ -164,6 +164,141 @@ __device__ __forceinline__ float wave_sum_f(float v) {
 }
 __device__ __forceinline__ float sgnf(float x) { return (x > 0.f) ? 1.f : ((x < 0.f) ? -1.f : 0.f); }
 
+// ---- the all-f32 InfoNCE passes' work list (losses.hip; here because the SpMM rider below cuts it too) ------------------
+constexpr int kNceSplits = 16;      // workspace is sized for this many key splits
+constexpr int kNceMaxProblems = 4;
+constexpr unsigned long long kLossUnreported = ~0ull;      // (see rows_finish: a loss-partial slot nobody has written yet)
+__host__ __device__ inline int64_t nce_pad(int64_t n) { return (n + 63) / 64 * 64; }
+
+// The row counts n_k of a step (unique users / items of the batch: ~1880 and ~1620 of 2048 on the Yelp shape) exist only on
+// the device, and the passes' work goes with n_k^2: a grid cut on the host for n_max runs 36 % more key blocks than the
+// batch holds and leaves a sixth of the CUs without a workgroup.  So the f32 passes launch one workgroup per CU and every
+// workgroup derives the SAME task list from the device counts: problem k is cut into qb_k = ceil(np_k / 128) query blocks
+// (8 waves x 16 queries) times splits_k key ranges of per_k 32-key blocks, with the block budget T per task the one that
+// minimises rounds(T) x T (rounds = tasks over workgroups; T >= kb_k / 16: the split partials' workspace holds 16).
+struct NcePlan {
+  int n[kNceMaxProblems], per[kNceMaxProblems], splits[kNceMaxProblems], first[kNceMaxProblems + 1];
+};
+constexpr int kNceQueryBlock = 128, kNceKeyBlock = 32, kNceMaxPer = 128;
+
+// The cut from the live counts n[0 .. kNceMaxProblems) (0: no such problem) on `slots` workgroups.  Host and device: the
+// passes' prep kernel (or the stage rider of the product before them) runs it once per step, srh_infonce_plan answers the
+// same question without a launch.
+// A task's 1 / l values sit in kNceMaxPer x 32 floats of LDS (NceF32::kLds), so the block budget never exceeds kNceMaxPer:
+// with n <= 65 536 (launch_infonce refuses more) t_min <= kNceMaxPer and a cut exists; what the budget leaves over
+// becomes more tasks than workgroups, which the passes' task loop strides over.
+__host__ __device__ inline void nce_plan(const int* n_live, int slots, NcePlan& p) {
+  int qb[kNceMaxProblems], kb[kNceMaxProblems];
+  int t_min = 1;
+  long long work = 0;
+#pragma unroll
+  for (int k = 0; k < kNceMaxProblems; ++k) {
+    const int n = n_live[k];
+    p.n[k] = n;
+    const int np = (int)nce_pad(n);
+    qb[k] = (np + kNceQueryBlock - 1) / kNceQueryBlock;
+    kb[k] = np / kNceKeyBlock;
+    const int need = (kb[k] + kNceSplits - 1) / kNceSplits;
+    t_min = t_min > need ? t_min : need;
+    work += (long long)qb[k] * kb[k];
+  }
+  const long long even = (work + slots - 1) / slots;
+  int t = even > t_min ? (even < kNceMaxPer ? (int)even : kNceMaxPer) : t_min;
+  int best_t = t;
+  long long best_cost = -1;
+  for (int it = 0; it < 32 && (t <= kNceMaxPer || it == 0); ++it, ++t) {
+    int tasks = 0;
+#pragma unroll
+    for (int k = 0; k < kNceMaxProblems; ++k) tasks += qb[k] * ((kb[k] + t - 1) / t);
+    const int rounds = (tasks + slots - 1) / slots;
+    const long long cost = (long long)rounds * t;
+    if (best_cost < 0 || cost < best_cost) { best_cost = cost; best_t = t; }
+    if (rounds <= 1) break;
+  }
+  p.first[0] = 0;
+#pragma unroll
+  for (int k = 0; k < kNceMaxProblems; ++k) {
+    const int sp = kb[k] > 0 ? (kb[k] + best_t - 1) / best_t : 0;
+    p.splits[k] = sp;
+    p.per[k] = sp > 0 ? (kb[k] + sp - 1) / sp : 0;       // the even cut of kb_k over its splits (<= best_t)
+    p.first[k + 1] = p.first[k] + qb[k] * sp;
+  }
+}
+
+// One row of an InfoNCE view as nce_prep_body (losses.hip) leaves it: x / max(|x|, 1e-12) (F.normalize's eps), |x| in
+// `norm`.  v: this lane's float4 of the row, held by an LPR-lane row-group.  The ONE definition of that arithmetic for the
+// prep kernel and the stage rider (pass 1 restates it on its own register layout: nce_tile_f32).
+template <int LPR>
+__device__ __forceinline__ float4 nce_unit_row(const float4 v, float& norm) {
+  const float ss = group_sum<LPR>(f4_dot(v, v));
+  norm = sqrtf(ss);
+  const float den = fmaxf(norm, 1e-12f);           // F.normalize eps
+  return make_float4(v.x / den, v.y / den, v.z / den, v.w / den);
+}
+
+// "nce stage": what the all-f32 InfoNCE passes need from before their first launch and that depends on nothing later than
+// the contrast table -- the key-side view v2n / norm2, the armed tickets and loss partials, the step's task plan -- done by
+// rider workgroups at the head of the product that READS that table (srh_spmm_f32_with_nce_stage), where nce_prep would
+// be a launch of its own.  Pass 1 then normalises its own queries (srh_bpr_infonce_fwd_bwd_staged).
+struct NceStageProblem {
+  const float* src2;          // the key-side table (rows idx[i])
+  const int32_t* idx;
+  const int32_t* d_n;
+  int n_max, np;
+  float *v2n, *norm2, *v1n, *norm1;
+  int32_t* ticket;
+  unsigned long long* losspart;
+};
+struct NceStageArgs {
+  NceStageProblem p[kNceMaxProblems];
+  NcePlan* plan;
+  int count, slots;
+  int gpx;                    // workgroups per problem: 256 threads = 4 waves of 64 / LPR rows each
+};
+// host: the rider's arguments for `count` problems whose workspaces lie back to back in ws (losses.hip: the carve is there)
+srh_status_t nce_stage_args(const srh_infonce_problem_t* problems, int count, int d, void* ws, NceStageArgs& out);
+// block: 0 .. count * gpx (more: nothing to do).  Same arithmetic and the same stores as nce_prep_body's key-side half.
+template <int LPR>
+__device__ __forceinline__ void nce_stage_body(const NceStageArgs& s, const unsigned block) {
+  constexpr int G = 64 / LPR;
+  const unsigned bz = block / (unsigned)s.gpx, bx = block % (unsigned)s.gpx;
+  if ((int)bz >= s.count) return;
+  const NceStageProblem& w = s.p[bz];
+  const int n = w.d_n ? min(*w.d_n, w.n_max) : w.n_max;
+  const int lane = threadIdx.x & 63, g = lane / LPR, sub = lane % LPR;
+  const int i = (int)((bx * 256u + threadIdx.x) >> 6) * G + g;
+  if (bx == 0) {
+    for (int k = threadIdx.x; k <= w.np / 16; k += 256) w.ticket[k] = 0;
+    for (int k = threadIdx.x; k < w.np; k += 256) w.losspart[k] = kLossUnreported;
+  }
+  if (bx == 0 && bz == 0 && threadIdx.x == 0) {
+    NcePlan plan;
+    int n_live[kNceMaxProblems];
+#pragma unroll
+    for (int k = 0; k < kNceMaxProblems; ++k) {
+      n_live[k] = 0;
+      if (k < s.count) n_live[k] = max(0, s.p[k].d_n ? min(*s.p[k].d_n, s.p[k].n_max) : s.p[k].n_max);
+    }
+    nce_plan(n_live, s.slots, plan);
+    *s.plan = plan;
+  }
+  const bool valid = i < n;
+  const int src = valid ? (w.idx ? w.idx[i] : i) : 0;
+  const float4 v = reinterpret_cast<const float4*>(w.src2)[(size_t)src * LPR + sub];
+  float norm;
+  float4 o = nce_unit_row<LPR>(v, norm);
+  if (!valid) o = f4_zero();
+  if (i < w.np) {
+    reinterpret_cast<float4*>(w.v2n)[(size_t)i * LPR + sub] = o;
+    if (sub == 0) w.norm2[i] = valid ? norm : 0.f;
+    // the query-side rows no query block of pass 1 covers (the plan cuts nce_pad(n) rows, the workspace holds np)
+    if (i >= (int)nce_pad(max(n, 0))) {
+      reinterpret_cast<float4*>(w.v1n)[(size_t)i * LPR + sub] = f4_zero();
+      if (sub == 0) w.norm1[i] = 0.f;
+    }
+  }
+}
+
 // first position in the ascending a[lo, hi) whose value is >= x (hi if there is none); a: global memory or LDS
 __device__ __forceinline__ int lower_bound_i32(const int32_t* a, int lo, int hi, int x) {
   while (lo < hi) {

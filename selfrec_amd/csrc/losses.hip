@@ -57,12 +57,17 @@ struct BprArgs {
   int n_blocks;
 };
 
-template <int LPR>
-__device__ __forceinline__ void bpr_phase1_body(const BprArgs& a, const unsigned block_id) {
+// HALVES = 2: a 512-thread workgroup runs two of the 256-thread "blocks" (workgroup wg -> blocks 2 wg, 2 wg + 1: the same
+// 16-pair grouping and the same part[block * 4 + k] records, so phase 2 / rows_finish add the same doubles in the same
+// order); s_part: 4 HALVES x 4 doubles of LDS.
+template <int LPR, int HALVES = 1>
+__device__ __forceinline__ void bpr_phase1_body(const BprArgs& a, const unsigned wg, double (*s_part)[4]) {
   constexpr int G = 64 / LPR;
   const int rows = a.d_n_rows ? min(*a.d_n_rows, a.B) : a.B;
   const int lane = threadIdx.x & 63, g = lane / LPR, sub = lane % LPR;
-  const int b = (int)((block_id * 256u + threadIdx.x) >> 6) * G + g;
+  const unsigned half = HALVES > 1 ? threadIdx.x >> 8 : 0u, tid = threadIdx.x & 255u;
+  const unsigned block_id = wg * HALVES + half;
+  const int b = (int)((block_id * 256u + tid) >> 6) * G + g;
   const bool valid = b < rows;
   const int bu = valid ? a.u_idx[b] : 0, bi = valid ? a.i_idx[b] : 0, bj = valid ? a.j_idx[b] : 0;
   const float4 u = reinterpret_cast<const float4*>(a.user)[(size_t)bu * LPR + sub];
@@ -86,7 +91,6 @@ __device__ __forceinline__ void bpr_phase1_body(const BprArgs& a, const unsigned
   double sn = valid ? (double)f4_dot(rn, rn) : 0.0;
   // same-address atomics serialise at ~11 ns each on this chip (2048 of them cost 22 us):
   // reduce inside the workgroup and leave one partial record per workgroup instead
-  __shared__ double s_part[4][4];
   l_part = wave_sum_d(l_part);
   su = wave_sum_d(su);
   sp = wave_sum_d(sp);
@@ -94,9 +98,9 @@ __device__ __forceinline__ void bpr_phase1_body(const BprArgs& a, const unsigned
   const int wv = threadIdx.x >> 6;
   if (lane == 0) { s_part[wv][0] = l_part; s_part[wv][1] = su; s_part[wv][2] = sp; s_part[wv][3] = sn; }
   __syncthreads();
-  if (threadIdx.x < 4)
-    a.part[(size_t)block_id * 4 + threadIdx.x] =
-        s_part[0][threadIdx.x] + s_part[1][threadIdx.x] + s_part[2][threadIdx.x] + s_part[3][threadIdx.x];
+  if (tid < 4 && (int)block_id < a.n_blocks)     // (an odd block count: the last workgroup's second half has no record)
+    a.part[(size_t)block_id * 4 + tid] =
+        s_part[4 * half + 0][tid] + s_part[4 * half + 1][tid] + s_part[4 * half + 2][tid] + s_part[4 * half + 3][tid];
 }
 
 template <int LPR>
@@ -166,7 +170,10 @@ __device__ __forceinline__ void bpr_phase2_body(const BprArgs& a, const unsigned
 }
 
 template <int LPR>
-__global__ __launch_bounds__(256) void bpr_phase1(BprArgs a) { bpr_phase1_body<LPR>(a, blockIdx.x); }
+__global__ __launch_bounds__(256) void bpr_phase1(BprArgs a) {
+  __shared__ double s_part[4][4];
+  bpr_phase1_body<LPR>(a, blockIdx.x, s_part);
+}
 template <int LPR>
 __global__ __launch_bounds__(256) void bpr_phase2(BprArgs a) { bpr_phase2_body<LPR>(a, blockIdx.x); }
 
@@ -292,7 +299,7 @@ __global__ __launch_bounds__(256) void l2_reg_bwd_kernel(L2Args a, const float* 
 // ---------------------------------------------------------------------------------------
 // InfoNCE
 // ---------------------------------------------------------------------------------------
-constexpr int kNceSplits = 16;      // workspace is sized for this many key splits
+// (kNceSplits, the workspace's key splits per query tile, and the f32 passes' task plan: common.h)
 constexpr float kNceKqScale = 32.0f;                                  // K / Q images hold 32 x (see nce_prep_body)
 constexpr float kNceInvKqScale2 = 1.0f / (kNceKqScale * kNceKqScale);   // the similarity product comes out 1024 x
 // Two build-time shape constants of the tile passes (tools/spmm_lab/build_alt.sh builds the other settings for an A/B;
@@ -325,15 +332,13 @@ constexpr int kNcePvTerms = SRH_NCE_PV_TERMS;
 // the multi-problem entry points; the environment variable SRH_NCE_SPLIT16 makes it the initial default).
 std::atomic<int> g_nce_precision{getenv("SRH_NCE_SPLIT16") ? SRH_NCE_SPLIT16 : SRH_NCE_F32};
 
-constexpr unsigned long long kLossUnreported = ~0ull;      // (see rows_finish: a loss-partial slot nobody has written yet)
-
 struct NceWs {
   float *v1n, *v2n, *norm1, *norm2, *opart, *opart2, *lpart, *invl;
   float* ediag;         // split path: exp(s_ii / tau - 1 / tau) as pass 1's MFMA saw it (the pair's own weight is kept out of
                         // the accumulated sums: see nce_tile_lds)
   double* losspart;     // one partial per finish wave
   int32_t* ticket;      // np/16 + 1 arrival counters (zeroed by nce_prep, re-armed by the last arriver)
-  struct NcePlan* plan; // problem 0's: the persistent passes' task list for this step (written by nce_prep)
+  NcePlan* plan;        // problem 0's: the persistent passes' task list for this step (written by nce_prep)
   float* etile;         // all-f32 passes, n <= kNceReuseMax: pass 1's weights e_ij, stored [key j][query i] (row stride np),
                         // so that pass 2 reads its A fragments back instead of recomputing the logits (NULL: recompute)
   // split-bf16 operand images of the two normalised views (hi = bf16(x), lo = bf16(x - hi)):
@@ -352,7 +357,6 @@ struct NceWs {
   float *g1, *g2;
   int g2_plain;         // g2's rows are this problem's alone: plain read-add-store
 };
-constexpr int kNceMaxProblems = 4;
 struct NceBatch {
   NceWs w[kNceMaxProblems];
   int count;
@@ -362,64 +366,7 @@ struct NceBatch {
   int f32_only;    // the prep kernel leaves the 16-bit operand images unwritten
 };
 
-__host__ __device__ inline int64_t nce_pad(int64_t n) { return (n + 63) / 64 * 64; }
-
-// ---- the all-f32 passes' work list ---------------------------------------------------------------------------------------
-// The row counts n_k of a step (unique users / items of the batch: ~1880 and ~1620 of 2048 on the Yelp shape) exist only on
-// the device, and the passes' work goes with n_k^2: a grid cut on the host for n_max runs 36 % more key blocks than the
-// batch holds and leaves a sixth of the CUs without a workgroup.  So the f32 passes launch one workgroup per CU and every
-// workgroup derives the SAME task list from the device counts: problem k is cut into qb_k = ceil(np_k / 128) query blocks
-// (8 waves x 16 queries) times splits_k key ranges of per_k 32-key blocks, with the block budget T per task the one that
-// minimises rounds(T) x T (rounds = tasks over workgroups; T >= kb_k / 16: the split partials' workspace holds 16).
-struct NcePlan {
-  int n[kNceMaxProblems], per[kNceMaxProblems], splits[kNceMaxProblems], first[kNceMaxProblems + 1];
-};
-constexpr int kNceQueryBlock = 128, kNceKeyBlock = 32, kNceMaxPer = 128;
 constexpr int kNceReuseMax = 8192;      // pass 1 keeps its n x n weights for pass 2 up to this n (256 MB per problem)
-
-
-// The cut from the live counts n[0 .. kNceMaxProblems) (0: no such problem) on `slots` workgroups.  Host and device: the
-// passes' prep kernel runs it once per step, srh_infonce_plan answers the same question without a launch.
-// A task's 1 / l values sit in kNceMaxPer x 32 floats of LDS (NceF32::kLds), so the block budget never exceeds kNceMaxPer:
-// with n <= 65 536 (launch_infonce refuses more) t_min <= kNceMaxPer and a cut exists; what the budget leaves over
-// becomes more tasks than workgroups, which the passes' task loop strides over.
-__host__ __device__ inline void nce_plan(const int* n_live, int slots, NcePlan& p) {
-  int qb[kNceMaxProblems], kb[kNceMaxProblems];
-  int t_min = 1;
-  long long work = 0;
-#pragma unroll
-  for (int k = 0; k < kNceMaxProblems; ++k) {
-    const int n = n_live[k];
-    p.n[k] = n;
-    const int np = (int)nce_pad(n);
-    qb[k] = (np + kNceQueryBlock - 1) / kNceQueryBlock;
-    kb[k] = np / kNceKeyBlock;
-    const int need = (kb[k] + kNceSplits - 1) / kNceSplits;
-    t_min = t_min > need ? t_min : need;
-    work += (long long)qb[k] * kb[k];
-  }
-  const long long even = (work + slots - 1) / slots;
-  int t = even > t_min ? (even < kNceMaxPer ? (int)even : kNceMaxPer) : t_min;
-  int best_t = t;
-  long long best_cost = -1;
-  for (int it = 0; it < 32 && (t <= kNceMaxPer || it == 0); ++it, ++t) {
-    int tasks = 0;
-#pragma unroll
-    for (int k = 0; k < kNceMaxProblems; ++k) tasks += qb[k] * ((kb[k] + t - 1) / t);
-    const int rounds = (tasks + slots - 1) / slots;
-    const long long cost = (long long)rounds * t;
-    if (best_cost < 0 || cost < best_cost) { best_cost = cost; best_t = t; }
-    if (rounds <= 1) break;
-  }
-  p.first[0] = 0;
-#pragma unroll
-  for (int k = 0; k < kNceMaxProblems; ++k) {
-    const int sp = kb[k] > 0 ? (kb[k] + best_t - 1) / best_t : 0;
-    p.splits[k] = sp;
-    p.per[k] = sp > 0 ? (kb[k] + sp - 1) / sp : 0;       // the even cut of kb_k over its splits (<= best_t)
-    p.first[k + 1] = p.first[k] + qb[k] * sp;
-  }
-}
 
 
 inline NceWs carve_nce(void* ws, int64_t n_max, int d) {
@@ -492,10 +439,8 @@ __device__ __forceinline__ void nce_prep_body(const NceBatch& batch, const unsig
   const bool valid = i < n;
   const int src = valid ? (idx ? idx[i] : i) : 0;
   float4 v = reinterpret_cast<const float4*>(V)[(size_t)src * LPR + sub];
-  const float ss = group_sum<LPR>(f4_dot(v, v));
-  const float norm = sqrtf(ss);
-  const float den = fmaxf(norm, 1e-12f);           // F.normalize eps
-  float4 o = make_float4(v.x / den, v.y / den, v.z / den, v.w / den);
+  float norm;
+  float4 o = nce_unit_row<LPR>(v, norm);
   if (!valid) o = f4_zero();
   if (in_pad) {
     reinterpret_cast<float4*>(out)[(size_t)i * LPR + sub] = o;
@@ -555,7 +500,8 @@ __global__ __launch_bounds__(256) void nce_prep(NceBatch batch) { nce_prep_body<
 // pair shares one launch (workgroups [0, n_bpr) take the BPR role) and overlaps instead of queueing.
 template <int LPR>
 __global__ __launch_bounds__(256) void nce_prep_bpr1(NceBatch batch, BprArgs bpr, int n_bpr, int gpx) {
-  if ((int)blockIdx.x < n_bpr) { bpr_phase1_body<LPR>(bpr, blockIdx.x); return; }
+  __shared__ double s_part[4][4];
+  if ((int)blockIdx.x < n_bpr) { bpr_phase1_body<LPR>(bpr, blockIdx.x, s_part); return; }
   const unsigned k = blockIdx.x - n_bpr;
   nce_prep_body<LPR>(batch, k % gpx, (k / gpx) & 1u, k / (2u * gpx));
 }
@@ -988,8 +934,18 @@ __device__ __forceinline__ void st_f1_wt(float* p, float v) {
   asm volatile("global_store_dword %0, %1, off sc1" ::"v"(p), "v"(v) : "memory");
 }
 
-template <int D, bool PASS2, bool REUSE>
-__global__ __launch_bounds__(512) void nce_tile_f32(NceBatch batch, float inv_tau) {
+// RAW (pass 1 of srh_bpr_infonce_fwd_bwd_staged: no prep launch ran): the key-side view, the plan and the armed counters
+// were left by the stage rider of an earlier product (nce_stage_body, common.h); the QUERY rows are read raw through idx and
+// normalised here, in the registers they are used from, to the bits nce_prep_body stores -- a lane holds the 16-byte chunks
+// sub = g + 4 t of its row, so group_sum<D / 4>'s xor butterfly over sub is lanes ^ 16, lanes ^ 32, then in-lane adds over t,
+// and every level is commutative.  The split-0 task of a query block stores the rows (v1n, norm1) for pass 2 and the finish.
+// Workgroups n_task_wg and up (the END of the grid: the task workgroups are dispatched first) run BPR phase 1, two of its
+// 256-thread blocks each, and leave before any ring code.
+// (One body, two kernels: nce_tile_f32<D, PASS2, REUSE> as every other path launches it, nce_pass1_raw_f32<D, REUSE> = RAW.)
+template <int D, bool PASS2, bool REUSE, bool RAW>
+__device__ __forceinline__ void nce_tile_f32_body(const NceBatch& batch, const float inv_tau, const BprArgs& bpr,
+                                                  const int n_task_wg) {
+  static_assert(!(RAW && PASS2), "raw queries: pass 1 only");
   constexpr int DQ = D / 4;            // k-steps of the S product (dims per lane)
   constexpr int NT = D / 16;           // 16-column n-tiles of the P.V product
   constexpr int NV = NT / 4;           // 16-byte chunks of a row a lane reads for the P.V product
@@ -1000,6 +956,13 @@ __global__ __launch_bounds__(512) void nce_tile_f32(NceBatch batch, float inv_ta
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   float* invl_s = reinterpret_cast<float*>(smem + Cfg::kSlots * Cfg::kBlockBytes);
   const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)smem;
+  if constexpr (RAW) {
+    if ((int)blockIdx.x >= n_task_wg) {
+      bpr_phase1_body<D / 4, 2>(bpr, blockIdx.x - n_task_wg, reinterpret_cast<double (*)[4]>(smem));
+      return;
+    }
+  }
+  const int task_stride = RAW ? n_task_wg : (int)gridDim.x;
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   SRH_STAMP(0);
   const NcePlan plan = *batch.w[0].plan;
@@ -1024,7 +987,7 @@ __global__ __launch_bounds__(512) void nce_tile_f32(NceBatch batch, float inv_ta
   }
 
   const int n_tasks = plan.first[kNceMaxProblems];
-  for (int task = blockIdx.x; task < n_tasks; task += gridDim.x) {
+  for (int task = blockIdx.x; task < n_tasks; task += task_stride) {
     int k = 0, first = 0, per = plan.per[0], splits = plan.splits[0], n = plan.n[0];
 #pragma unroll
     for (int q = 1; q < kNceMaxProblems; ++q)
@@ -1064,10 +1027,20 @@ __global__ __launch_bounds__(512) void nce_tile_f32(NceBatch batch, float inv_ta
     };
     // the ring's first chunk first: the longest latency of the prologue; the query rows and (pass 2) the 1 / l fold go under
     // it, the run-ahead chunks after them (so that "all but the 4 LPB youngest" below names exactly chunk 0 and these)
+    // (RAW: the query's table row number is asked for FIRST and waited for only after every chunk of the prologue has been
+    // requested: the ring never queues behind the extra round trip -- with the row loads right behind chunk 0 the compiler
+    // put the wait for the row number between the chunk's two requests, and chunks 1 .. 3 behind the rows)
+    int qsrc = 0;
+    if constexpr (RAW) {
+      const int qi = max(min(q0 + c16, n - 1), 0);
+      qsrc = w.idx ? w.idx[qi] : qi;
+      asm volatile("" ::: "memory");
+    }
     issue_chunk(0);
     constexpr bool kLogits = !(PASS2 && REUSE);                     // this pass forms the logits itself
     float qreg[DQ];
-    if constexpr (kLogits) {
+    float qnorm = 0.f;
+    if constexpr (!RAW && kLogits) {
       const float* src = Qv + (size_t)min(q0 + c16, np - 1) * D + 4 * g;
 #pragma unroll
       for (int t = 0; t < KQ; ++t) {
@@ -1096,7 +1069,42 @@ __global__ __launch_bounds__(512) void nce_tile_f32(NceBatch batch, float inv_ta
     // the matrix pipe idle: all eight waves meet at the barrier, issue their two direct loads -- 60-185 cycles each -- and
     // wait out an LDS round trip at the same time; a 7-block task has three of them.)
     const bool resident = nblk <= Cfg::kSlots;
-    if (resident) {
+    if constexpr (RAW) {
+      if (resident) issue_chunk(3);
+      asm volatile("" ::: "memory");      // (keeps the row loads, which wait for qsrc, behind the chunks' requests)
+      float4 qraw[KQ];
+      {
+        const float* src = w.src1 + (size_t)qsrc * D + 4 * g;
+#pragma unroll
+        for (int t = 0; t < KQ; ++t) qraw[t] = *reinterpret_cast<const float4*>(src + 16 * t);
+      }
+      float ps[KQ];
+#pragma unroll
+      for (int t = 0; t < KQ; ++t) {
+        ps[t] = f4_dot(qraw[t], qraw[t]);
+        ps[t] += __shfl_xor(ps[t], 16);                             // group_sum's level 1 (sub ^ 1 = g ^ 1)
+        ps[t] += __shfl_xor(ps[t], 32);                             // level 2
+      }
+#pragma unroll
+      for (int m = 1; m < KQ; m <<= 1) {                            // levels 4 and up: sub ^ 4 m = t ^ m
+        float nx[KQ];
+#pragma unroll
+        for (int t = 0; t < KQ; ++t) nx[t] = ps[t] + ps[t ^ m];
+#pragma unroll
+        for (int t = 0; t < KQ; ++t) ps[t] = nx[t];
+      }
+      const float norm = sqrtf(ps[0]);
+      const float den = fmaxf(norm, 1e-12f);                        // F.normalize eps
+      const bool qvalid = q0 + c16 < n;
+      qnorm = qvalid ? norm : 0.f;
+#pragma unroll
+      for (int t = 0; t < KQ; ++t) {
+        qreg[4 * t + 0] = qvalid ? qraw[t].x / den : 0.f; qreg[4 * t + 1] = qvalid ? qraw[t].y / den : 0.f;
+        qreg[4 * t + 2] = qvalid ? qraw[t].z / den : 0.f; qreg[4 * t + 3] = qvalid ? qraw[t].w / den : 0.f;
+      }
+      // (the rows were the youngest loads: with them, every chunk requested above is in)
+      asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    } else if (resident) {
       issue_chunk(3);
       // chunk 0 has landed once all but the 6 LPB youngest loads are back (lgkmcnt: the 1 / l stores)
       if constexpr (LPB == 1) asm volatile("s_waitcnt vmcnt(6) lgkmcnt(0)\n\ts_barrier" ::: "memory");
@@ -1339,8 +1347,27 @@ __global__ __launch_bounds__(512) void nce_tile_f32(NceBatch batch, float inv_ta
       lsum += __shfl_xor(lsum, 32);
       if (g == 0) const_cast<float*>(lpart)[(size_t)split * stride + qrow] = lsum;
     }
+    if constexpr (RAW) {
+      // the block's normalised queries, once: pass 2's keys and the finish read them (rows >= n: zeros, as the prep kernel's)
+      if (split == 0 && qrow < (int)w.np) {
+        float* dst = w.v1n + (size_t)qrow * D + 4 * g;
+#pragma unroll
+        for (int t = 0; t < KQ; ++t)
+          *reinterpret_cast<float4*>(dst + 16 * t) = make_float4(qreg[4 * t], qreg[4 * t + 1], qreg[4 * t + 2], qreg[4 * t + 3]);
+        if (g == 0) w.norm1[qrow] = qnorm;
+      }
+    }
     SRH_STAMP(4);
   }
+}
+
+template <int D, bool PASS2, bool REUSE>
+__global__ __launch_bounds__(512) void nce_tile_f32(NceBatch batch, float inv_tau) {
+  nce_tile_f32_body<D, PASS2, REUSE, false>(batch, inv_tau, BprArgs{}, 0);
+}
+template <int D, bool REUSE>
+__global__ __launch_bounds__(512) void nce_pass1_raw_f32(NceBatch batch, float inv_tau, BprArgs bpr, int n_task_wg) {
+  nce_tile_f32_body<D, false, REUSE, true>(batch, inv_tau, bpr, n_task_wg);
 }
 
 // One finish for both passes (used with nce_tile_lds): folds the split partials, turns them into the
@@ -1676,7 +1703,7 @@ void launch_rows_finish(const NceBatch& batch, const NceFinishArgs& fa, const Bp
 template <int D>
 srh_status_t launch_infonce(const srh_infonce_problem_t* pr, int count, float tau, float loss_scale, double* loss,
                             void* ws, hipStream_t st, int precision, const BprArgs* bpr = nullptr,
-                            const SegArgs* seg = nullptr) {
+                            const SegArgs* seg = nullptr, bool staged = false) {
   constexpr int LPR = D / 4, G = 64 / LPR;
   NceBatch batch{};
   batch.count = count;
@@ -1716,7 +1743,14 @@ srh_status_t launch_infonce(const srh_infonce_problem_t* pr, int count, float ta
   dim3 gp((np_max / G + 3) / 4, 2, count);
   BprArgs bp{};
   int n_bpr = 0;
-  if (bpr) {
+  // staged (srh_bpr_infonce_fwd_bwd_staged): no prep launch -- the stage rider of an earlier product left v2n, the plan and
+  // the armed counters; pass 1 normalises its own queries and carries BPR phase 1 at the end of its grid
+  SRH_REQUIRE(!staged || (f32 && bpr && D <= 128),
+              "bpr_infonce_fwd_bwd_staged: the all-f32 passes (d = 64 / 128) with a BPR problem only");
+  if (staged) {
+    bp = *bpr;
+    n_bpr = bp.n_blocks = ((bp.B + G - 1) / G + 3) / 4;
+  } else if (bpr) {
     bp = *bpr;
     n_bpr = bp.n_blocks = ((bp.B + G - 1) / G + 3) / 4;
     nce_prep_bpr1<LPR><<<n_bpr + (int)(gp.x * 2 * count), 256, 0, st>>>(batch, bp, n_bpr, (int)gp.x);
@@ -1747,17 +1781,22 @@ srh_status_t launch_infonce(const srh_infonce_problem_t* pr, int count, float ta
       (void)hipFuncSetAttribute((const void*)nce_tile_f32<D, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, kLds);
       (void)hipFuncSetAttribute((const void*)nce_tile_f32<D, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, kLds);
       (void)hipFuncSetAttribute((const void*)nce_tile_f32<D, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, kLds);
+      (void)hipFuncSetAttribute((const void*)nce_pass1_raw_f32<D, false>, hipFuncAttributeMaxDynamicSharedMemorySize, kLds);
+      (void)hipFuncSetAttribute((const void*)nce_pass1_raw_f32<D, true>, hipFuncAttributeMaxDynamicSharedMemorySize, kLds);
       return true;
     }();
     (void)attr_set;
     bool reuse = true;                     // pass 1 keeps its weights for pass 2 (every problem has the n x n array)
     for (int k = 0; k < count; ++k) reuse = reuse && batch.w[k].etile != nullptr;
+    const int bpr_wg = (n_bpr + 1) / 2;      // (staged: 512-thread workgroups of two BPR phase-1 blocks behind the tasks')
     if (reuse) {
-      nce_tile_f32<D, false, true><<<grid_f32, 512, kLds, st>>>(batch, inv_tau);
+      if (staged) nce_pass1_raw_f32<D, true><<<grid_f32 + bpr_wg, 512, kLds, st>>>(batch, inv_tau, bp, grid_f32);
+      else nce_tile_f32<D, false, true><<<grid_f32, 512, kLds, st>>>(batch, inv_tau);
       SRH_LAUNCH_CHECK();
       nce_tile_f32<D, true, true><<<grid_f32, 512, kLds, st>>>(batch, inv_tau);
     } else {
-      nce_tile_f32<D, false, false><<<grid_f32, 512, kLds, st>>>(batch, inv_tau);
+      if (staged) nce_pass1_raw_f32<D, false><<<grid_f32 + bpr_wg, 512, kLds, st>>>(batch, inv_tau, bp, grid_f32);
+      else nce_tile_f32<D, false, false><<<grid_f32, 512, kLds, st>>>(batch, inv_tau);
       SRH_LAUNCH_CHECK();
       nce_tile_f32<D, true, false><<<grid_f32, 512, kLds, st>>>(batch, inv_tau);
     }
@@ -1808,6 +1847,35 @@ static srh_status_t seg_args(const srh_batch_segments_t* g, int n_problems, SegA
 }
 
 }  // namespace
+
+// the stage rider's view of the problems and their workspace (common.h; spmm.hip launches it): the same carve and the same
+// limits as launch_infonce's all-f32 path
+srh_status_t srh::nce_stage_args(const srh_infonce_problem_t* pr, int count, int d, void* ws, NceStageArgs& out) {
+  SRH_REQUIRE(pr && ws, "spmm_f32_with_nce_stage: null argument");
+  SRH_REQUIRE(count >= 1 && count <= kNceMaxProblems, "spmm_f32_with_nce_stage: 1..%d problems", kNceMaxProblems);
+  SRH_REQUIRE(d == 64 || d == 128, "spmm_f32_with_nce_stage: the all-f32 passes serve d = 64 / 128, not %d", d);
+  out = NceStageArgs{};
+  out.count = count;
+  out.slots = srh::cu_count();
+  const int G = 64 / (d / 4);
+  int np_max = 0;
+  char* cursor = reinterpret_cast<char*>(ws);
+  for (int k = 0; k < count; ++k) {
+    SRH_REQUIRE(pr[k].d_v2 && pr[k].n > 0 && pr[k].n < (int64_t(1) << 24), "spmm_f32_with_nce_stage: bad problem %d", k);
+    const NceWs w = carve_nce(cursor, pr[k].n, d);
+    cursor += srh_infonce_ws_bytes(pr[k].n, d);
+    if (w.np / kNceKeyBlock > (int64_t)kNceSplits * kNceMaxPer) {
+      srh::set_error("spmm_f32_with_nce_stage: the all-f32 MFMA path serves n <= %d", kNceSplits * kNceMaxPer * kNceKeyBlock);
+      return SRH_ERR_UNSUPPORTED;
+    }
+    out.p[k] = NceStageProblem{pr[k].d_v2, pr[k].d_idx, pr[k].d_n, (int)pr[k].n, (int)w.np, w.v2n, w.norm2, w.v1n, w.norm1,
+                               w.ticket, reinterpret_cast<unsigned long long*>(w.losspart)};
+    if (k == 0) out.plan = w.plan;
+    np_max = std::max(np_max, (int)w.np);
+  }
+  out.gpx = (np_max / G + 3) / 4;
+  return SRH_OK;
+}
 
 extern "C" {
 
@@ -1949,7 +2017,7 @@ srh_status_t srh_infonce_plan(const int32_t* n, int32_t count, int32_t slots, in
 
 static srh_status_t infonce_entry(const srh_infonce_problem_t* problems, int32_t n_problems, int32_t d, float tau,
                                   float loss_scale, double* d_loss, void* d_ws, int32_t precision, void* stream,
-                                  const BprArgs* bpr, const SegArgs* seg = nullptr) {
+                                  const BprArgs* bpr, const SegArgs* seg = nullptr, bool staged = false) {
   SRH_REQUIRE(precision == SRH_NCE_DEFAULT || precision == SRH_NCE_SPLIT16 || precision == SRH_NCE_F32,
               "infonce_fwd_bwd: unknown precision %d", precision);
   if (precision == SRH_NCE_DEFAULT) {
@@ -1979,9 +2047,9 @@ static srh_status_t infonce_entry(const srh_infonce_problem_t* problems, int32_t
     return SRH_ERR_UNSUPPORTED;
   }
   hipStream_t st = srh::as_stream(stream);
-  if (d == 64) return launch_infonce<64>(problems, n_problems, tau, loss_scale, d_loss, d_ws, st, precision, bpr, seg);
-  if (d == 128) return launch_infonce<128>(problems, n_problems, tau, loss_scale, d_loss, d_ws, st, precision, bpr, seg);
-  return launch_infonce<256>(problems, n_problems, tau, loss_scale, d_loss, d_ws, st, precision, bpr, seg);
+  if (d == 64) return launch_infonce<64>(problems, n_problems, tau, loss_scale, d_loss, d_ws, st, precision, bpr, seg, staged);
+  if (d == 128) return launch_infonce<128>(problems, n_problems, tau, loss_scale, d_loss, d_ws, st, precision, bpr, seg, staged);
+  return launch_infonce<256>(problems, n_problems, tau, loss_scale, d_loss, d_ws, st, precision, bpr, seg, staged);
 }
 
 #ifdef SRH_NCEF32_STAMPS
@@ -2005,9 +2073,9 @@ srh_status_t srh_infonce_fwd_bwd_multi(const srh_infonce_problem_t* problems, in
   return infonce_entry(problems, n_problems, d, tau, loss_scale, d_loss, d_ws, precision, stream, nullptr);
 }
 
-srh_status_t srh_bpr_infonce_fwd_bwd(const srh_bpr_problem_t* b, const srh_infonce_problem_t* problems,
-                                     int32_t n_problems, int32_t d, float tau, float cl_scale, double* d_cl_loss,
-                                     void* d_nce_ws, int32_t precision, void* stream) {
+static srh_status_t bpr_infonce_entry(const srh_bpr_problem_t* b, const srh_infonce_problem_t* problems,
+                                      int32_t n_problems, int32_t d, float tau, float cl_scale, double* d_cl_loss,
+                                      void* d_nce_ws, int32_t precision, void* stream, bool staged) {
   SRH_REQUIRE(b, "bpr_infonce_fwd_bwd: null bpr problem");
   SRH_REQUIRE(b->d_user && b->d_item && b->d_reg_user && b->d_reg_item && b->d_u_idx && b->d_i_idx && b->d_j_idx,
               "bpr_infonce_fwd_bwd: null input");
@@ -2021,7 +2089,20 @@ srh_status_t srh_bpr_infonce_fwd_bwd(const srh_bpr_problem_t* b, const srh_infon
   SegArgs sg{};
   if (b->seg)
     if (srh_status_t st = seg_args(b->seg, n_problems, sg)) return st;
-  return infonce_entry(problems, n_problems, d, tau, cl_scale, d_cl_loss, d_nce_ws, precision, stream, &a, b->seg ? &sg : nullptr);
+  return infonce_entry(problems, n_problems, d, tau, cl_scale, d_cl_loss, d_nce_ws, precision, stream, &a, b->seg ? &sg : nullptr,
+                       staged);
+}
+
+srh_status_t srh_bpr_infonce_fwd_bwd(const srh_bpr_problem_t* b, const srh_infonce_problem_t* problems,
+                                     int32_t n_problems, int32_t d, float tau, float cl_scale, double* d_cl_loss,
+                                     void* d_nce_ws, int32_t precision, void* stream) {
+  return bpr_infonce_entry(b, problems, n_problems, d, tau, cl_scale, d_cl_loss, d_nce_ws, precision, stream, false);
+}
+
+srh_status_t srh_bpr_infonce_fwd_bwd_staged(const srh_bpr_problem_t* b, const srh_infonce_problem_t* problems,
+                                            int32_t n_problems, int32_t d, float tau, float cl_scale, double* d_cl_loss,
+                                            void* d_nce_ws, void* stream) {
+  return bpr_infonce_entry(b, problems, n_problems, d, tau, cl_scale, d_cl_loss, d_nce_ws, SRH_NCE_F32, stream, true);
 }
 
 srh_status_t srh_bpr_l2_fwd_bwd_p(const srh_bpr_problem_t* b, int32_t d, void* stream) {

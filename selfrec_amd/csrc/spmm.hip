@@ -522,13 +522,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
                                                         const Heavy* __restrict__ heavy,
                                                         const int32_t* __restrict__ slot_owner,
                                                         int32_t* __restrict__ tickets, DevEpilogue ep,
-                                                        const int n_fetch, const srh_batch_fetch_args_t rider) {
+                                                        const int n_fetch, const srh_batch_fetch_args_t rider,
+                                                        const int rider_kind, const srh::NceStageArgs stage) {
   constexpr int G = 64 / LPR;          // row-groups per wave
   constexpr int CH = 16 * G;           // entries per coop chunk
   // srh_spmm_f32_with_fetch: the first n_fetch workgroups (a multiple of 8: every task keeps its XCD) stage the step's
-  // batch instead -- nothing in this product reads what they write
+  // batch instead -- nothing in this product reads what they write.  srh_spmm_f32_with_nce_stage (rider_kind 1): they stage
+  // the InfoNCE passes' key-side view, counters and plan from the table this product reads (nce_stage_body, common.h)
   if ((int)blockIdx.x < n_fetch) {
-    srh::batch_fetch_body(rider, (int)blockIdx.x, n_fetch);
+    if (rider_kind == 1) srh::nce_stage_body<LPR>(stage, blockIdx.x);
+    else srh::batch_fetch_body(rider, (int)blockIdx.x, n_fetch);
     return;
   }
   const int wave = __builtin_amdgcn_readfirstlane((int)(((blockIdx.x - n_fetch) * 256u + threadIdx.x) >> 6));
@@ -1372,14 +1375,14 @@ enum class Rows { Plain, ColMask, Probe, LatePf, Floor, Adam };
 template <Rows F>
 static bool launch_rows(const srh_spmm_plan_t* plan, int32_t d, const int32_t* d_indices, const float* d_vals, const float* d_x,
                         float* d_y, const DevEpilogue& ep, int n_fetch, const srh_batch_fetch_args_t& fetch_args,
-                        hipStream_t st) {
+                        int rider_kind, const srh::NceStageArgs& stage, hipStream_t st) {
   const int gi = rows_gi(d);
 #define SRH_LAUNCH_ROWS(LPR)                                                                                            \
   spmm_rows_kernel<LPR, F == Rows::ColMask, F == Rows::Probe, F == Rows::LatePf, F == Rows::Floor, F == Rows::Adam>    \
       <<<(plan->n_run[gi] + 3) / 4 + n_fetch, 256, 0, st>>>(                                                             \
           plan->d_tasks64[gi], plan->n_run[gi], d_indices, d_vals, reinterpret_cast<const float4*>(d_x),                \
           reinterpret_cast<float4*>(d_y), reinterpret_cast<float4*>(plan->d_partial), plan->d_heavy, plan->d_slot_owner, \
-          plan->d_tickets, ep, n_fetch, fetch_args)
+          plan->d_tickets, ep, n_fetch, fetch_args, rider_kind, stage)
   switch (d) {
     case 64: SRH_LAUNCH_ROWS(16); break;
     // (late prefetch was measured, and is built, at d = 64 only)
@@ -1394,9 +1397,18 @@ static bool launch_rows(const srh_spmm_plan_t* plan, int32_t d, const int32_t* d
 // every product launch: srh_spmm_f32 / _with_fetch, the probe (d_stamps) and the gather bound (floor_only)
 static srh_status_t spmm_launch(const srh_spmm_plan_t* plan, const int32_t* d_indices, const float* d_vals, const float* d_x,
                                 float* d_y, int32_t d, const srh_spmm_epilogue_t* epi, const srh_batch_fetch_args_t* fetch,
-                                unsigned long long* d_stamps, void* stream, bool floor_only = false) {
+                                unsigned long long* d_stamps, void* stream, bool floor_only = false,
+                                const srh::NceStageArgs* nce_stage = nullptr) {
   srh_batch_fetch_args_t fetch_args{};
-  int n_fetch = 0;
+  srh::NceStageArgs stage{};
+  int n_fetch = 0, rider_kind = 0;
+  if (nce_stage) {
+    SRH_REQUIRE(!fetch && (d == 64 || d == 128) && !floor_only && !d_stamps,
+                "spmm_f32_with_nce_stage: d = 64 / 128, one rider per launch, not under the probes");
+    stage = *nce_stage;
+    rider_kind = 1;
+    n_fetch = (stage.count * stage.gpx + 7) / 8 * 8;       // (a multiple of 8: every task keeps its XCD)
+  }
   if (fetch) {
     SRH_REQUIRE(d >= 64 && !(epi && (epi->d_col_mark || epi->d_row_mark)),
                 "spmm_f32_with_fetch: d >= 64, and the product must not depend on the batch's marks");
@@ -1439,7 +1451,7 @@ static srh_status_t spmm_launch(const srh_spmm_plan_t* plan, const int32_t* d_in
                                                         : Rows::Plain;
       bool launched = false;
 #define SRH_ROWS_CASE(F) \
-  case Rows::F: launched = launch_rows<Rows::F>(plan, d, d_indices, d_vals, d_x, d_y, ep, n_fetch, fetch_args, st); break
+  case Rows::F: launched = launch_rows<Rows::F>(plan, d, d_indices, d_vals, d_x, d_y, ep, n_fetch, fetch_args, rider_kind, stage, st); break
       switch (flavour) {
         SRH_ROWS_CASE(Floor);
         SRH_ROWS_CASE(Probe);
@@ -1656,6 +1668,20 @@ srh_status_t srh_spmm_f32_with_fetch(const srh_spmm_plan_t* plan, const int32_t*
                                      const srh_spmm_epilogue_t* epi, const srh_batch_fetch_args_t* fetch, void* stream) {
   (void)d_indptr;  // the schedule in `plan` already encodes the row extents
   return spmm_launch(plan, d_indices, d_vals, d_x, d_y, d, epi, fetch, nullptr, stream);
+}
+
+srh_status_t srh_spmm_f32_with_nce_stage(const srh_spmm_plan_t* plan, const int32_t* d_indptr, const int32_t* d_indices,
+                                         const float* d_vals, const float* d_x, float* d_y, int32_t d,
+                                         const srh_spmm_epilogue_t* epi, const srh_infonce_problem_t* problems,
+                                         int32_t n_problems, void* d_nce_ws, void* stream) {
+  (void)d_indptr;
+  srh::NceStageArgs stage;
+  if (srh_status_t rc = srh::nce_stage_args(problems, n_problems, d, d_nce_ws, stage)) return rc;
+  // the rider runs beside the product: it may read what the product reads, nothing it writes
+  for (int k = 0; k < n_problems; ++k)
+    SRH_REQUIRE(problems[k].d_v2 != d_y, "spmm_f32_with_nce_stage: problem %d reads the table this product writes", k);
+  SRH_REQUIRE(!(epi && (epi->flags & SRH_EPI_ADAM)), "spmm_f32_with_nce_stage: not on the optimiser's launch");
+  return spmm_launch(plan, d_indices, d_vals, d_x, d_y, d, epi, nullptr, nullptr, stream, false, &stage);
 }
 
 srh_status_t srh_spmm_f32_probe(const srh_spmm_plan_t* plan, const int32_t* d_indices, const float* d_vals, const float* d_x,

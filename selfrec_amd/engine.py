@@ -208,6 +208,13 @@ class FusedTrainer:
         # batch_fetch as a rider of the step's first product (see _step_front): models whose step starts with a plain
         # srh_spmm_f32 launch of a layer that is not the last
         self.ride_fetch = single and self.L >= 2 and self.d >= 64 and model in ("LightGCN", "XSimGCL", "SimGCL")
+        # The InfoNCE prep launch folded into its neighbours (see _nce_staged): the key-side view, the counters and the
+        # task plan ride on the product that READS the contrast table Y[layer_cl - 1] (so a later product must exist:
+        # layer_cl < L), pass 1 normalises its own queries and carries the BPR scores.  All-f32 passes, whole rows here.
+        # SRH_NCE_PREP=1: the prep launch as before (A/B; tools/prepless_ab.py flips _prep_launch in one process).
+        self.nce_stage_ok = (single and not self.colx.split and model == "XSimGCL" and self.d in (64, 128)
+                             and 1 <= self.layer_cl < self.L)
+        self._prep_launch = os.environ.get("SRH_NCE_PREP", "0") == "1"
         # Adam inside the LAST backward product's row epilogue (SRH_EPI_ADAM): the finished gradient row updates its
         # parameter row where it is produced -- no 18 MB gradient written and read back, no separate 21 us pass; the same
         # launch clears the batch rows of the sparse gradient buffers and advances the cursor (what Adam's pass did).  Whole
@@ -570,8 +577,21 @@ class FusedTrainer:
             kw["d_valid"] = self.d_valid
         return kw
 
+    def _nce_staged(self):
+        """This step runs without the InfoNCE prep launch (decided per step build: nce_precision can change)."""
+        return self.nce_stage_ok and self.nce_precision == "f32" and not self._prep_launch
+
+    def _xsimgcl_problems(self, views=None):
+        """The step's two InfoNCE problems (users, positive items): final rows against the contrast layer's.
+        views: (T, GT, ix) of colx.loss_views where the caller already has them."""
+        T, GT, ix = views if views is not None else self.colx.loss_views(self)[:3]
+        CL = self.E0 if self.layer_cl == 0 else self.Y[self.layer_cl - 1]
+        # (gCL's rows: the user-side problem names user rows, the item-side one item rows, nobody else writes them)
+        return [(T(self.F), T(CL), ix["uniq_u"], self.B, self.meta[1:2], GT(self.gF), GT(self.gCL), True),
+                (T(self.F), T(CL), ix["uniq_i"], self.B, self.meta[2:3], GT(self.gF), GT(self.gCL), True)]
+
     def _forward_pass(self, adj, Ys, F, *, perturbed, include_ego, batch_rows_only=False, need_last=False,
-                      start_layer=0, noises=None, call_base=None):
+                      start_layer=0, noises=None, call_base=None, nce_stage_at=None):
         """L SpMMs; layer k's epilogue perturbs (optional) and the last one also writes the
         layer mean into F.  Returns nothing; the CL view of XSimGCL is Ys[l*-1] (or E0).
         batch_rows_only: the last layer's output (and F) feed nothing but the batch losses, so
@@ -605,6 +625,9 @@ class FusedTrainer:
             rider = {}
             if getattr(self, "_rider", None) is not None:
                 rider, self._rider = {"fetch": self._rider}, None
+            if nce_stage_at is not None and k == nce_stage_at:
+                # (this product reads the contrast table Ys[k - 1]; the batch's lists were staged by an earlier launch)
+                rider = {"nce_stage": (self._xsimgcl_problems(), self.nce_ws)}
             ops.spmm(adj, x, out=self._loc(Ys[k]), epilogue=ops.make_epilogue(**kw) if kw else None,
                      **({"pattern": True} if vf and k > 0 else {}), **rider)
             if k < L - 1 or need_last:
@@ -803,7 +826,8 @@ class FusedTrainer:
                                    batch_rows_only=True, start_layer=1)
         elif m != "MF":
             self._forward_pass(adj, self.Y, self.F, perturbed=(m == "XSimGCL"), include_ego=include_ego,
-                               batch_rows_only=True, need_last=(m == "XSimGCL" and self.layer_cl == self.L))
+                               batch_rows_only=True, need_last=(m == "XSimGCL" and self.layer_cl == self.L),
+                               nce_stage_at=self.layer_cl if m == "XSimGCL" and self._nce_staged() else None)
         if m == "SGL" and not sgl_shared_first:
             for vi, v in enumerate(self.views):
                 self._forward_pass(self.view_adj[vi], v["Y"], v["F"], perturbed=False, include_ego=include_ego,
@@ -856,11 +880,9 @@ class FusedTrainer:
                    precision=self.nce_precision)
         # ---- recommendation + contrastive loss (a-5..a-8)
         if m == "XSimGCL":
-            CL = self.E0 if self.layer_cl == 0 else self.Y[self.layer_cl - 1]
-            ops.bpr_infonce(*bpr_in, **bpr, bpr_ws=self.bpr_ws, **nce, **seg, **({"nce_rows": 1} if seg else {}), problems=[
-                # (gCL's rows: the user-side problem names user rows, the item-side one item rows, nobody else writes them)
-                (T(F), T(CL), ix["uniq_u"], self.B, nuu_dev, GT(self.gF), GT(self.gCL), True),
-                (T(F), T(CL), ix["uniq_i"], self.B, nui_dev, GT(self.gF), GT(self.gCL), True)])
+            staged = {"staged": True} if self._nce_staged() else {}
+            ops.bpr_infonce(*bpr_in, **bpr, bpr_ws=self.bpr_ws, **nce, **seg, **({"nce_rows": 1} if seg else {}), **staged,
+                            problems=self._xsimgcl_problems((T, GT, ix)))
         elif m in ("SimGCL", "SGL"):
             a, b = self.views
             if m == "SimGCL":

@@ -428,10 +428,12 @@ def make_epilogue(*, perturb_eps=None, noise=None, rng_seed=0, rng_offset=0, rng
 
 
 def spmm(csr: DeviceCSR, x: torch.Tensor, out: torch.Tensor | None = None, epilogue: SpmmEpilogue | None = None,
-         pattern: bool = False, fetch=None):
+         pattern: bool = False, fetch=None, nce_stage=None):
     """out = csr @ x (+ fused epilogue).  x: (n_cols, d) fp32.  pattern=True: the structure with every stored entry 1
     (no value stream; d >= 64) -- with row scaling in the epilogue this is the value-free form of D^-1/2 A D^-1/2.
-    fetch: a BatchFetchArgs (batch_fetch_args) -- the launch also stages the step's batch (srh_spmm_f32_with_fetch)."""
+    fetch: a BatchFetchArgs (batch_fetch_args) -- the launch also stages the step's batch (srh_spmm_f32_with_fetch).
+    nce_stage: (problems, nce_ws) as bpr_infonce(..., staged=True) will get them later in the step -- the launch also
+    stages the InfoNCE passes' key-side view, counters and plan (srh_spmm_f32_with_nce_stage)."""
     if x.dim() != 2 or x.shape[0] != csr.shape[1]:
         raise SelfrecHipError(f"spmm: x has shape {tuple(x.shape)}, expected ({csr.shape[1]}, d)")
     d = int(x.shape[1])
@@ -440,7 +442,14 @@ def spmm(csr: DeviceCSR, x: torch.Tensor, out: torch.Tensor | None = None, epilo
     common = (csr._plan, _p(csr.indptr, torch.int32), _p(csr.indices, torch.int32),
               None if pattern else _p(csr.vals, torch.float32, "vals"), _p(x, torch.float32, "x"),
               _p(out, torch.float32, "out"), d, C.byref(epilogue) if epilogue is not None else None)
-    if fetch is not None:
+    if nce_stage is not None:
+        if fetch is not None:
+            raise SelfrecHipError("spmm: one rider per launch (fetch or nce_stage)")
+        problems, nce_ws = nce_stage
+        arr = _infonce_problems(problems, d, nce_ws)
+        check(_lib.load().srh_spmm_f32_with_nce_stage(*common, arr, len(problems), _p(nce_ws), _stream()),
+              "srh_spmm_f32_with_nce_stage")
+    elif fetch is not None:
         check(_lib.load().srh_spmm_f32_with_fetch(*common, C.byref(fetch), _stream()), "srh_spmm_f32_with_fetch")
     else:
         check(_lib.load().srh_spmm_f32(*common, _stream()), "srh_spmm_f32")
@@ -762,6 +771,22 @@ def infonce_fwd_bwd(v1, v2, idx, n, *, n_dev=None, tau, loss_scale, loss, g1, g2
                                           _p(ws), _stream()), "srh_infonce_fwd_bwd")
 
 
+def _infonce_problems(problems, d, ws):
+    """[(v1, v2, idx, n_max, n_dev, g1, g2[, g2_exclusive]), ...] -> srh_infonce_problem_t[]; ws must hold them all."""
+    lib = _lib.load()
+    arr = (_lib.InfonceProblem * len(problems))()
+    need = 0
+    for k, (v1, v2, idx, n, n_dev, g1, g2, *rest) in enumerate(problems):
+        arr[k].d_v1, arr[k].d_v2 = _p(v1, torch.float32), _p(v2, torch.float32)
+        arr[k].d_idx, arr[k].n, arr[k].d_n = _p(idx, torch.int32), int(n), _p(n_dev, torch.int32)
+        arr[k].d_g1, arr[k].d_g2 = _p(g1, torch.float32), _p(g2, torch.float32)
+        arr[k].g2_exclusive = int(bool(rest[0])) if rest else 0
+        need += int(lib.srh_infonce_ws_bytes(n, d))
+    if ws.numel() * ws.element_size() < need:
+        raise SelfrecHipError(f"infonce workspace too small: {ws.numel() * ws.element_size()} < {need}")
+    return arr
+
+
 def infonce_multi(problems, *, d, tau, loss_scale, loss, ws, precision=None):
     """problems: [(v1, v2, idx, n_max, n_dev, g1, g2[, g2_exclusive]), ...] evaluated by one set of launches."""
     lib = _lib.load()
@@ -782,10 +807,12 @@ def infonce_multi(problems, *, d, tau, loss_scale, loss, ws, precision=None):
 
 def bpr_infonce(user, item, reg_user, reg_item, u_idx, i_idx, j_idx, *, batch, n_rows_dev=None, reg_coef,
                 reg_include_neg, loss_scale, g_user, g_item, greg_user, greg_item, losses, bpr_ws,
-                problems, tau, cl_scale, cl_loss, nce_ws, precision=None, seg=None, nce_rows=0):
+                problems, tau, cl_scale, cl_loss, nce_ws, precision=None, seg=None, nce_rows=0, staged=False):
     """bpr_l2_fwd_bwd + infonce_multi with their O(batch) kernels sharing launches (srh_bpr_infonce_fwd_bwd).
     seg / nce_rows: the batch's row -> slot lists and how the problems name those rows (srh_batch_segments_t): every
-    gradient row is then written once, by the row group that owns it, in slot order -- no float atomics."""
+    gradient row is then written once, by the row group that owns it, in slot order -- no float atomics.
+    staged: an earlier product of the step carried spmm(..., nce_stage=(problems, nce_ws)) -- no prep launch
+    (srh_bpr_infonce_fwd_bwd_staged: all-f32 arithmetic, d = 64 / 128)."""
     lib = _lib.load()
     d = int(user.shape[1])
     b = _bpr_problem(user, item, reg_user, reg_item, u_idx, i_idx, j_idx, batch, n_rows_dev, reg_coef, reg_include_neg,
@@ -800,6 +827,13 @@ def bpr_infonce(user, item, reg_user, reg_item, u_idx, i_idx, j_idx, *, batch, n
         need += int(lib.srh_infonce_ws_bytes(n, d))
     if nce_ws.numel() * nce_ws.element_size() < need:
         raise SelfrecHipError(f"infonce workspace too small: {nce_ws.numel() * nce_ws.element_size()} < {need}")
+    if staged:
+        if precision != "f32":
+            raise SelfrecHipError("bpr_infonce(staged=True): the all-f32 passes only (precision='f32')")
+        check(lib.srh_bpr_infonce_fwd_bwd_staged(C.byref(b), arr, len(problems), d, float(tau), float(cl_scale),
+                                                 _p(cl_loss, torch.float64), _p(nce_ws), _stream()),
+              "srh_bpr_infonce_fwd_bwd_staged")
+        return
     check(lib.srh_bpr_infonce_fwd_bwd(C.byref(b), arr, len(problems), d, float(tau), float(cl_scale),
                                       _p(cl_loss, torch.float64), _p(nce_ws), _nce_mode(precision), _stream()),
           "srh_bpr_infonce_fwd_bwd")

@@ -832,7 +832,7 @@ int lab_spmm_custom(void* h, const srh_spmm_plan_t* plan, const void* d_tasks, i
     srh_batch_fetch_args_t no_rider{};
     spmm_rows_kernel<16, false><<<blocks, 256, 0, st>>>(
         tasks, n_tasks, d_indices, d_vals, reinterpret_cast<const float4*>(d_x), reinterpret_cast<float4*>(d_y),
-        reinterpret_cast<float4*>(plan->d_partial), plan->d_heavy, plan->d_slot_owner, plan->d_tickets, ep, 0, no_rider);
+        reinterpret_cast<float4*>(plan->d_partial), plan->d_heavy, plan->d_slot_owner, plan->d_tickets, ep, 0, no_rider, 0, srh::NceStageArgs{});
   }
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
@@ -877,7 +877,7 @@ int lab_spmm(void* h, const srh_spmm_plan_t* plan, const int32_t* d_indices, con
     srh_batch_fetch_args_t no_rider{};                                                                                \
     spmm_rows_kernel<16, false><<<blocks, 256, 0, st>>>(                                                              \
         plan->d_tasks64[1], n, d_indices, VALS, reinterpret_cast<const float4*>(d_x), reinterpret_cast<float4*>(d_y), \
-        reinterpret_cast<float4*>(plan->d_partial), plan->d_heavy, plan->d_slot_owner, plan->d_tickets, ep, 0, no_rider); \
+        reinterpret_cast<float4*>(plan->d_partial), plan->d_heavy, plan->d_slot_owner, plan->d_tickets, ep, 0, no_rider, 0, srh::NceStageArgs{}); \
   } while (0)
     case 75: LAB_PRODUCT(d_vals); break;          /* the product kernel launched from here (canonical task list) */
     case 76: LAB_PRODUCT(nullptr); break;         /* ... as a pattern product (no value stream): vs all-ones values */
