@@ -1078,6 +1078,60 @@ int64_t srh_tri_nd_ws_bytes(int64_t n, int32_t d, int32_t k);
 srh_status_t srh_tri_nd_fwd_bwd(const srh_tri_nd_args_t* args, void* d_ws, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * (a-20) MHCN -- the self-gates, the channel attention and the hierarchical mutual-information loss of
+ * model/graph/MHCN.py:79-93 and 159-181.  All arithmetic fp32; no float atomics: every reduction over rows runs in fixed
+ * chunks whose partials are summed in chunk order, so a call returns the same bits every time.  d = 64 or 128 (zero-pad
+ * narrower rows: a padded column has x = 0 and changes no result), anything else is SRH_ERR_UNSUPPORTED with a message;
+ * any n >= 0 (n == 0 writes only the weight gradients / the loss, as zeros).
+ *
+ * srh_gate_fwd_f32: Y_c = X (.) sigmoid(X W_c + b_c), c < n_gates (1..4).  d_x (n x d), d_w (n_gates x d x d, the x @ W
+ *   layout), d_b (n_gates x d); d_y (n_gates x n x d) is WRITTEN.  The product runs on v_mfma_f32_16x16x4_f32, every gate
+ *   from one read of X.
+ * srh_gate_bwd_f32: with dZ_c = dY_c (.) X (.) S_c (1 - S_c) (S is recomputed, not saved):
+ *   d_gx = sum_c (dY_c (.) S_c + dZ_c W_c^T), d_gw[c] = X^T dZ_c, d_gb[c] = the column sums of dZ_c; all WRITTEN.
+ *   d_ws >= srh_gate_bwd_ws_bytes(n, d, n_gates) (0 for an unsupported shape).
+ * srh_chan_mix_fwd_f32: w_c[r] = E_c[r] . q, s[r] = softmax_c w_c[r], out[r] = sum_c s_c[r] E_c[r] + beta X[r] (d_x may be
+ *   NULL: no addend).  d_out (n x d) and d_score (n x 3) are WRITTEN.  One wave per row.
+ * srh_chan_mix_bwd_f32: from d_gout (n x d) and the forward's d_score: d_ge1..3 (n x d), d_gx = beta d_gout (optional, may
+ *   be NULL) and d_gq (d) are WRITTEN.  The scores carry no gradient of their own.  d_ws >= srh_chan_mix_bwd_ws_bytes(n, d).
+ * srh_mim_fwd_bwd: em, edge (n x d; edge = H em, made by the caller), row permutations p1, p2, p3 (int32, n) and column
+ *   permutations c2, c3 (int32, d; the identity over pad columns).  rcs(E; c, p)[r][j] = E[p[r]][c[j]],
+ *   sp(x) = max(x, 0) + log1p(exp(-|x|)), g = the column mean of edge;
+ *     pos = em_r . edge_r, n1 = em_{p1[r]} . edge_r, n2 = rcs(edge; c2, p2)_r . em_r, gp = edge_r . g,
+ *     gn = rcs(edge; c3, p3)_r . g;   d_loss = loss_scale * sum_r sp(n1 - pos) + sp(n2 - n1) + sp(gn - gp)
+ *   (sp(-x) = -log(sigmoid(x)) wherever the latter is finite in float32).  d_loss (one double), d_gem and d_gedge (n x d,
+ *   scaled by loss_scale, the gradient through g included) are WRITTEN.  Every scatter of the backward pass is a gather
+ *   through the inverse permutation, built on the device in the workspace; an index outside its range contributes nothing.
+ *   d_ws >= srh_mim_ws_bytes(n, d).
+ * ---------------------------------------------------------------------------------- */
+srh_status_t srh_gate_fwd_f32(const float* d_x, const float* d_w, const float* d_b, int64_t n, int32_t d, int32_t n_gates,
+                              float* d_y, void* stream);
+int64_t srh_gate_bwd_ws_bytes(int64_t n, int32_t d, int32_t n_gates);
+srh_status_t srh_gate_bwd_f32(const float* d_x, const float* d_w, const float* d_b, const float* d_gy, int64_t n, int32_t d,
+                              int32_t n_gates, float* d_gx, float* d_gw, float* d_gb, void* d_ws, void* stream);
+srh_status_t srh_chan_mix_fwd_f32(const float* d_e1, const float* d_e2, const float* d_e3, const float* d_q,
+                                  const float* d_x, float beta, int64_t n, int32_t d, float* d_out, float* d_score,
+                                  void* stream);
+int64_t srh_chan_mix_bwd_ws_bytes(int64_t n, int32_t d);
+srh_status_t srh_chan_mix_bwd_f32(const float* d_e1, const float* d_e2, const float* d_e3, const float* d_q,
+                                  const float* d_score, const float* d_gout, float beta, int64_t n, int32_t d, float* d_ge1,
+                                  float* d_ge2, float* d_ge3, float* d_gx, float* d_gq, void* d_ws, void* stream);
+typedef struct srh_mim_args {
+  const float* d_em;
+  const float* d_edge;
+  const int32_t* d_row_perm[3];
+  const int32_t* d_col_perm[2];
+  int64_t n;
+  int32_t d;
+  float loss_scale;
+  double* d_loss;
+  float* d_gem;
+  float* d_gedge;
+} srh_mim_args_t;
+int64_t srh_mim_ws_bytes(int64_t n, int32_t d);
+srh_status_t srh_mim_fwd_bwd(const srh_mim_args_t* args, void* d_ws, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * (f-1) Dataset files -> id arrays -- replaces the python loops of data/loader.py:22-33
  * (FileIO.load_data_set: one "user item weight" line per interaction, single-space separated)
  * and data/ui_graph.py:29-45 (ids in first-appearance order of the training file; test pairs kept

@@ -77,6 +77,13 @@ class TriNdArgs(C.Structure):
                 ("d_gaug", C.c_void_p), ("d_pos", C.c_void_p)]
 
 
+class MimArgs(C.Structure):
+    """struct srh_mim_args (include/selfrec_hip.h)."""
+    _fields_ = [("d_em", C.c_void_p), ("d_edge", C.c_void_p), ("d_row_perm", C.c_void_p * 3), ("d_col_perm", C.c_void_p * 2),
+                ("n", C.c_int64), ("d", C.c_int32), ("loss_scale", C.c_float), ("d_loss", C.c_void_p), ("d_gem", C.c_void_p),
+                ("d_gedge", C.c_void_p)]
+
+
 SCALAR_WS_BYTES = 64        # SRH_SCALAR_WS_BYTES
 
 
@@ -215,6 +222,14 @@ SIGNATURES = {
     "srh_rows_l2norm_bwd_f32": (_i32, [_vp, _vp, _vp, _i64, _i32, _vp, _vp]),
     "srh_tri_nd_ws_bytes": (_i64, [_i64, _i32, _i32]),
     "srh_tri_nd_fwd_bwd": (_i32, [C.POINTER(TriNdArgs), _vp, _vp]),
+    "srh_gate_fwd_f32": (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp]),
+    "srh_gate_bwd_ws_bytes": (_i64, [_i64, _i32, _i32]),
+    "srh_gate_bwd_f32": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "srh_chan_mix_fwd_f32": (_i32, [_vp, _vp, _vp, _vp, _vp, _f32, _i64, _i32, _vp, _vp, _vp]),
+    "srh_chan_mix_bwd_ws_bytes": (_i64, [_i64, _i32]),
+    "srh_chan_mix_bwd_f32": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _f32, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "srh_mim_ws_bytes": (_i64, [_i64, _i32]),
+    "srh_mim_fwd_bwd": (_i32, [C.POINTER(MimArgs), _vp, _vp]),
     "srh_adam_step": (_i32, [_vp, _vp, _vp, _vp, _i64, _i64, _vp, _f32, _f32, _f32, _f32, _vp]),
     "srh_adam_step_reset": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _vp, _f32, _f32, _f32, _f32, _vp, _i32, _vp, _vp, _vp]),
     "srh_score_mask_topk": (_i32, [_vp, _vp, _i64, _vp, _i64, _i32, _vp, _vp, _i32, _vp, _i64, _vp, _vp, _vp]),

@@ -5,10 +5,11 @@
     python -m selfrec_amd.main BERT4Rec --synthetic beauty-seq
     python -m selfrec_amd.main CL4SRec --synthetic beauty-seq
     python -m selfrec_amd.main SEPT --synthetic douban-book
+    python -m selfrec_amd.main MHCN --synthetic douban-book
 
 ``--synthetic SHAPE`` writes a generated dataset of that shape (selfrec_amd/synth.py) to the
 paths the config names, if they do not exist yet -- the reference's dataset files are not
-redistributable.  A config that names a ``social.data`` file (SEPT) gets a generated trust file the same way.
+redistributable.  A config that names a ``social.data`` file (SEPT, MHCN) gets a generated trust file the same way.
 """
 import argparse
 import os
@@ -18,7 +19,7 @@ from . import synth
 from .SELFRec import SELFRec
 from .util.conf import ModelConf
 
-MODELS = ['MF', 'LightGCN', 'XSimGCL', 'SimGCL', 'SGL', 'DirectAU', 'MixGCF', 'BUIR', 'SelfCF', 'NCL', 'UserKNN', 'ItemKNN', 'SSL4Rec', 'SASRec', 'BERT4Rec', 'CL4SRec', 'SEPT']
+MODELS = ['MF', 'LightGCN', 'XSimGCL', 'SimGCL', 'SGL', 'DirectAU', 'MixGCF', 'BUIR', 'SelfCF', 'NCL', 'UserKNN', 'ItemKNN', 'SSL4Rec', 'SASRec', 'BERT4Rec', 'CL4SRec', 'SEPT', 'MHCN']
 
 
 def main(argv=None):
