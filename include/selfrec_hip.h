@@ -1078,6 +1078,56 @@ int64_t srh_tri_nd_ws_bytes(int64_t n, int32_t d, int32_t k);
 srh_status_t srh_tri_nd_fwd_bwd(const srh_tri_nd_args_t* args, void* d_ws, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * (a-21) MixGCF -- the hop mixing of model/graph/MixGCF.py:96-114 (negative_mixup): pick, mix and row gradients.
+ * H = n_hops item tables T_k (n_items x d float32, row-major; any 16-byte aligned address, e.g. the item rows of a
+ * (users + items) x d table), C = n_negs candidates per pair: pair b owns d_neg[b C .. b C + C - 1].  All arithmetic fp32,
+ * no float atomics, nothing waits on the host: a call returns the same bits every time.
+ *
+ * srh_mixup_fwd_f32: for every pair b < B and hop k < H, with p = T_k[pos[b]] and n_c = T_k[neg[b C + c]]:
+ *     m_c = alpha_{k,b,c} (.) p + (1 - alpha_{k,b,c}) (.) n_c   (per element: fma(alpha, p, (1 - alpha) n))
+ *     s_c = u_b . m_c,   pick[k][b] = argmax_c s_c
+ *   (an exact float32 tie goes to the lowest c; the running maximum starts at -inf).  WRITTEN: d_neg_out[b] =
+ *   (sum_k m_pick) / H and d_pos_out[b] = (sum_k T_k[pos[b]]) / H, both B x d and summed in hop order, and d_pick (int32,
+ *   H x B).  The mixed candidates, alpha and the scores are never written to memory.
+ * alpha: either INJECTED -- d_alpha[k] (B x C x d, values in [0, 1)) for every k < H -- or, with every d_alpha[k] NULL,
+ *   DRAWN by the counter RNG of srh_spmm_epilogue (lowbias32 / counter_rng4 / u01): row (k, b, c) uses counter
+ *   rng_counter + (k B + b) C + c and float4 number q of the row uses sub = q, so the draws of one call are the
+ *   (H B C) x d block of counters [rng_counter, rng_counter + H B C).
+ * srh_mixup_bwd_f32: from d_g_neg and d_g_pos (B x d; either may be NULL = zero), the forward's d_pick and the same alpha
+ *   source (alpha* = alpha of the picked candidate, recomputed), every d_grad[k] (n_items x d) is WRITTEN whole -- zero
+ *   outside the touched rows -- with
+ *     row pos[b]                  += (g_pos[b] + alpha*_{k,b} (.) g_neg[b]) / H
+ *     row neg[b C + pick[k][b]]   += ((1 - alpha*_{k,b}) (.) g_neg[b]) / H
+ *   (per element fma(alpha*, g_neg, g_pos) / H and ((1 - alpha*) g_neg) / H, the division correctly rounded),
+ *   summed per (hop, item) row in ascending b, a pair's positive before its negative, by one writer.  u takes no gradient
+ *   (the choice is detached).  d_ws >= srh_mixup_bwd_ws_bytes(B, n_hops) (0 for an unsupported shape or B <= 0).
+ * Served: d a multiple of 4 in 4..256, 1 <= n_hops <= SRH_MIXUP_MAX_HOPS, n_negs >= 1, any B >= 0 (B == 0: the backward
+ *   writes the zero tables, the forward nothing); anything else is SRH_ERR_UNSUPPORTED with a message.  An index outside
+ *   [0, n_items) is never dereferenced: such a candidate scores -inf, such a positive reads as a zero row, and neither
+ *   takes a gradient.  The forward reads d_table, the backward d_grad; the other array may be left zeroed.
+ * ---------------------------------------------------------------------------------- */
+#define SRH_MIXUP_MAX_HOPS 8
+typedef struct srh_mixup_args {
+  const float* d_table[SRH_MIXUP_MAX_HOPS];
+  const float* d_alpha[SRH_MIXUP_MAX_HOPS];
+  float* d_grad[SRH_MIXUP_MAX_HOPS];
+  const int32_t* d_pos;
+  const int32_t* d_neg;
+  int64_t n_items;
+  int64_t B;
+  int32_t n_hops;
+  int32_t n_negs;
+  int32_t d;
+  uint64_t rng_seed;
+  uint64_t rng_counter;
+} srh_mixup_args_t;
+srh_status_t srh_mixup_fwd_f32(const srh_mixup_args_t* args, const float* d_u, float* d_pos_out, float* d_neg_out,
+                               int32_t* d_pick, void* stream);
+int64_t srh_mixup_bwd_ws_bytes(int64_t B, int32_t n_hops);
+srh_status_t srh_mixup_bwd_f32(const srh_mixup_args_t* args, const int32_t* d_pick, const float* d_g_pos,
+                               const float* d_g_neg, void* d_ws, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * (a-20) MHCN -- the self-gates, the channel attention and the hierarchical mutual-information loss of
  * model/graph/MHCN.py:79-93 and 159-181.  All arithmetic fp32; no float atomics: every reduction over rows runs in fixed
  * chunks whose partials are summed in chunk order, so a call returns the same bits every time.  d = 64 or 128 (zero-pad

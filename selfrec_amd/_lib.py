@@ -84,6 +84,17 @@ class MimArgs(C.Structure):
                 ("d_gedge", C.c_void_p)]
 
 
+SRH_MIXUP_MAX_HOPS = 8
+
+
+class MixupArgs(C.Structure):
+    """struct srh_mixup_args (include/selfrec_hip.h)."""
+    _fields_ = [("d_table", C.c_void_p * SRH_MIXUP_MAX_HOPS), ("d_alpha", C.c_void_p * SRH_MIXUP_MAX_HOPS),
+                ("d_grad", C.c_void_p * SRH_MIXUP_MAX_HOPS), ("d_pos", C.c_void_p), ("d_neg", C.c_void_p),
+                ("n_items", C.c_int64), ("B", C.c_int64), ("n_hops", C.c_int32), ("n_negs", C.c_int32), ("d", C.c_int32),
+                ("rng_seed", C.c_uint64), ("rng_counter", C.c_uint64)]
+
+
 SCALAR_WS_BYTES = 64        # SRH_SCALAR_WS_BYTES
 
 
@@ -230,6 +241,9 @@ SIGNATURES = {
     "srh_chan_mix_bwd_f32": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _f32, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "srh_mim_ws_bytes": (_i64, [_i64, _i32]),
     "srh_mim_fwd_bwd": (_i32, [C.POINTER(MimArgs), _vp, _vp]),
+    "srh_mixup_fwd_f32": (_i32, [C.POINTER(MixupArgs), _vp, _vp, _vp, _vp, _vp]),
+    "srh_mixup_bwd_ws_bytes": (_i64, [_i64, _i32]),
+    "srh_mixup_bwd_f32": (_i32, [C.POINTER(MixupArgs), _vp, _vp, _vp, _vp, _vp]),
     "srh_adam_step": (_i32, [_vp, _vp, _vp, _vp, _i64, _i64, _vp, _f32, _f32, _f32, _f32, _vp]),
     "srh_adam_step_reset": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _vp, _f32, _f32, _f32, _f32, _vp, _i32, _vp, _vp, _vp]),
     "srh_score_mask_topk": (_i32, [_vp, _vp, _i64, _vp, _i64, _i32, _vp, _vp, _i32, _vp, _i64, _vp, _vp, _vp]),

@@ -3,6 +3,14 @@ Yelp2018-shaped graph with a device synchronisation after every statement of int
 (GPU box only; tools/gpu_session.sh stage ``oplevel``).
 
     python tools/oplevel_probe.py BUIR 40
+
+MixGCF's hop mixing has two routes (``engine.mixup``: csrc/mixgcf.hip or the reference's torch expression); ``--ab`` times
+them against each other at the conf's shape (Yelp2018-shaped synthetic graph, B = 2048, 64 candidates, 3 layers, d = 64),
+ALTERNATED inside one process -- hip, torch, hip, torch ... -- so that a drift of the machine lands on both: the mixing
+forward and its backward on fixed hop tables (HIP events), one whole step (wall time between fences), and the peak memory
+of each.  Warm-up first; median, min and max of the repeats.
+
+    python tools/oplevel_probe.py MixGCF --ab [--repeats 30] [--out profiles/mixgcf_probe.json]
 """
 import sys
 import time
@@ -118,7 +126,111 @@ def probe_generic(rec, steps):
     ck.report(steps)
 
 
+def probe_mixgcf_ab(repeats, out):
+    import json
+    import os
+    import random
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    from bert4rec_probe import peak_extra_bytes
+    from sept_probe import alternating, stats
+    from selfrec_amd import ops
+    from selfrec_amd.model.graph.MixGCF import MixGCF, mixup_torch
+    from selfrec_amd.util.sampler import next_batch_pairwise
+    ops.require_gpu()
+    B, C, L, d = 2048, 64, 3, 64
+    tu, ti, su, si, _, _ = synth.make_dataset("yelp2018")
+
+    def make(route):
+        conf = ModelConf({"training.set": "./none", "test.set": "./none", "model": {"name": "MixGCF", "type": "graph"},
+                          "item.ranking.topN": [10, 20], "embedding.size": d, "max.epoch": 1, "batch.size": B,
+                          "learning.rate": 0.001, "reg.lambda": 0.0001, "output": "./results/",
+                          "MixGCF": {"n_layer": L, "n_negs": C}, "engine.mixup": route})
+        torch.manual_seed(0)
+        m = MixGCF(conf, synth.as_triples(tu, ti), synth.as_triples(su, si))
+        m.model.cuda().train()
+        assert m.model.mixup == route
+        return m
+    models = {r: make(r) for r in ("hip", "torch")}
+    base = models["hip"]
+    random.seed(1)
+    idx = [torch.from_numpy(a).cuda() for a in next(iter(next_batch_pairwise(base.data, B, C, as_arrays=True)))]
+    user, pos, neg = idx
+    res = {"shape": {"dataset": "yelp2018 (synthetic)", "users": base.data.user_num, "items": base.data.item_num, "B": B,
+                     "n_negs": C, "n_layer": L, "d": d}}
+
+    # ---- the mixing alone, on fixed hop tables ----------------------------------------------------------------------------
+    with torch.no_grad():
+        users, item_hops = base.model.hop_tables()
+        u = users[user].contiguous()
+        item_hops = [h.contiguous() for h in item_hops]
+    g = torch.Generator().manual_seed(0)
+    gp, gn = torch.randn(B, d, generator=g).cuda(), torch.randn(B, d, generator=g).cuda()
+
+    def forward(route):
+        hops = [h.clone().requires_grad_(True) for h in item_hops]
+        if route == "hip":
+            return ops.MixupFn.apply(u, pos, neg, C, None, 1234, 0, *hops)[:2]
+        return mixup_torch(u, hops, pos, neg, C)
+    res["mixup_fwd_ms"] = alternating({r: (lambda r=r: forward(r)) for r in ("hip", "torch")}, 5, repeats)
+    ts = {"hip": [], "torch": []}
+    for k in range(5 + repeats):
+        for r in ts:
+            outs = forward(r)
+            t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            t0.record()
+            torch.autograd.backward(list(outs), [gp, gn])
+            t1.record()
+            t1.synchronize()
+            if k >= 5:
+                ts[r].append(t0.elapsed_time(t1))
+    res["mixup_bwd_ms"] = {r: stats(v) for r, v in ts.items()}
+
+    def fwd_bwd(route):
+        torch.autograd.backward(list(forward(route)), [gp, gn])
+    res["mixup_peak_extra_bytes"] = {r: peak_extra_bytes(lambda r=r: fwd_bwd(r)) for r in ("hip", "torch")}
+
+    # ---- the whole step -----------------------------------------------------------------------------------------------------
+    steps = {}
+    for name, m in models.items():
+        opt = torch.optim.Adam(m.model.parameters(), lr=1e-3)
+
+        def step(m=m, opt=opt):
+            loss = m.batch_loss(*idx)
+            opt.zero_grad()
+            loss.backward()
+            opt.step()
+        steps[name] = step
+    res["step_wall_ms"] = alternating(steps, 5, repeats, wall=True)
+    res["step_peak_extra_bytes"] = {name: peak_extra_bytes(fn) for name, fn in steps.items()}
+    peak = {}
+    for name, fn in steps.items():
+        torch.cuda.synchronize()
+        torch.cuda.reset_peak_memory_stats()
+        fn()
+        torch.cuda.synchronize()
+        peak[name] = int(torch.cuda.max_memory_allocated())
+    res["step_max_memory_allocated"] = peak
+    med = lambda key, r: res[key][r]["median"]  # noqa: E731
+    res["hip_over_torch"] = {k: med(k, "hip") / med(k, "torch") for k in ("mixup_fwd_ms", "mixup_bwd_ms", "step_wall_ms")}
+    res["device"] = torch.cuda.get_device_name(0)
+    print(json.dumps(res, indent=1))
+    os.makedirs(os.path.dirname(out) or ".", exist_ok=True)
+    with open(out, "w") as f:
+        json.dump(res, f, indent=1)
+
+
 if __name__ == "__main__":
+    if "--ab" in sys.argv:
+        import argparse
+        ap = argparse.ArgumentParser()
+        ap.add_argument("model", choices=["MixGCF"])
+        ap.add_argument("--ab", action="store_true")
+        ap.add_argument("--repeats", type=int, default=30)
+        ap.add_argument("--out", default="profiles/mixgcf_probe.json")
+        args = ap.parse_args()
+        assert args.repeats >= 5
+        probe_mixgcf_ab(args.repeats, args.out)
+        sys.exit(0)
     name = sys.argv[1] if len(sys.argv) > 1 else "BUIR"
     steps = int(sys.argv[2]) if len(sys.argv) > 2 else 40
     rec = build(name)
