@@ -316,11 +316,16 @@ srh_status_t srh_dataset_sizes(const srh_dataset_t* ds, int64_t* h_sizes5) {
 srh_status_t srh_dataset_copy_ids(const srh_dataset_t* ds, int32_t* h_train_u, int32_t* h_train_i, float* h_train_w,
                                   int32_t* h_test_u, int32_t* h_test_i) {
   SRH_REQUIRE(ds, "dataset_copy_ids: null handle");
-  if (h_train_u) memcpy(h_train_u, ds->train_u.data(), sizeof(int32_t) * ds->train_u.size());
-  if (h_train_i) memcpy(h_train_i, ds->train_i.data(), sizeof(int32_t) * ds->train_i.size());
-  if (h_train_w) memcpy(h_train_w, ds->train_w.data(), sizeof(float) * ds->train_w.size());
-  if (h_test_u) memcpy(h_test_u, ds->test_u.data(), sizeof(int32_t) * ds->test_u.size());
-  if (h_test_i) memcpy(h_test_i, ds->test_i.data(), sizeof(int32_t) * ds->test_i.size());
+  // (an empty vector's data() may be null, and memcpy from null is undefined even for 0 bytes: an empty train file, or no
+  // kept test pairs -- every load without a test file)
+  auto copy = [](auto* dst, const auto& src) {
+    if (dst && !src.empty()) memcpy(dst, src.data(), sizeof(src[0]) * src.size());
+  };
+  copy(h_train_u, ds->train_u);
+  copy(h_train_i, ds->train_i);
+  copy(h_train_w, ds->train_w);
+  copy(h_test_u, ds->test_u);
+  copy(h_test_i, ds->test_i);
   return SRH_OK;
 }
 
