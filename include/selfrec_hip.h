@@ -152,6 +152,8 @@ srh_status_t srh_mt19937_uniform_f32(uint32_t* h_mt624, int32_t* pos, int64_t n,
  * numpy computes it; integral degrees below table_len are looked up there, which makes the
  * values bit-identical to the reference's np.power(rowsum, -0.5) (numpy's fp32 pow is not
  * correctly rounded, so no device formula can match it in every last bit).
+ * n_rows < 2^31; each kernel is one launch up to 2^25 rows and one per 2^25 rows above (a launch
+ * holds fewer than 2^32 work-items at one wave per row).
  * ---------------------------------------------------------------------------------- */
 srh_status_t srh_adj_sym_normalize(int64_t n_rows, const int32_t* d_indptr,
                                    const int32_t* d_indices, const int32_t* d_edge_id,

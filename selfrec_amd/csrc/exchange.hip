@@ -130,9 +130,9 @@ srh_status_t srh_batch_pack(const srh_batch_lists_t* lists, int32_t n_tables, co
     SRH_REQUIRE(d_tables[k], "batch_pack: null table %d", k);
     t.src[k] = d_tables[k];
   }
+  // (total >= 5B: it also covers the a + c <= 2B threads that write d_cat_idx)
   const int64_t total = (int64_t)kSegs * l.B * (dl / 4) * n_tables;
-  const int64_t threads = total > 2 * (int64_t)l.B ? total : 2 * (int64_t)l.B;
-  pack_kernel<<<(unsigned)((threads + 255) / 256), 256, 0, srh::as_stream(stream)>>>(
+  pack_kernel<<<(unsigned)((total + 255) / 256), 256, 0, srh::as_stream(stream)>>>(
       l, t, n_tables, dl / 4, reinterpret_cast<float4*>(d_send), d_cat_idx, d_n_cat);
   SRH_LAUNCH_CHECK();
   return SRH_OK;

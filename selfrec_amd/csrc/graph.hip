@@ -13,15 +13,25 @@
 namespace {
 using namespace srh;
 
-__global__ __launch_bounds__(256) void degree_kernel(int n_rows, const int32_t* __restrict__ indptr,
+// One wave per row, four rows per block.  A dispatch counts its work-items in 32 bits, so a launch covers at most kRowsPerLaunch
+// rows (2^31 work-items) starting at row0; the row is formed from the block index in 64 bits, never from a global thread index
+// (blockIdx.x * 256 wraps in 32 bits from row 2^26 on).
+constexpr int64_t kRowsPerLaunch = int64_t(1) << 25;
+
+__device__ __forceinline__ int wave_row(int64_t row0, int n_rows) {
+  const int64_t row = row0 + (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  return row < n_rows ? (int)row : -1;
+}
+
+__global__ __launch_bounds__(256) void degree_kernel(int64_t row0, int n_rows, const int32_t* __restrict__ indptr,
                                                      const int32_t* __restrict__ edge_id,
                                                      const float* __restrict__ weight,
                                                      const uint8_t* __restrict__ keep,
                                                      const float* __restrict__ table, int table_len,
                                                      float* __restrict__ dinv_rows) {
   float* dinv = dinv_rows;       // (already offset to this shard's first row)
-  const int row = (int)((blockIdx.x * 256u + threadIdx.x) >> 6);
-  if (row >= n_rows) return;
+  const int row = wave_row(row0, n_rows);
+  if (row < 0) return;
   const int lane = threadIdx.x & 63;
   const int s = indptr[row], e = indptr[row + 1];
   float acc = 0.f;
@@ -40,15 +50,15 @@ __global__ __launch_bounds__(256) void degree_kernel(int n_rows, const int32_t* 
   }
 }
 
-__global__ __launch_bounds__(256) void normalize_kernel(int n_rows, const int32_t* __restrict__ indptr,
+__global__ __launch_bounds__(256) void normalize_kernel(int64_t row0, int n_rows, const int32_t* __restrict__ indptr,
                                                         const int32_t* __restrict__ indices,
                                                         const int32_t* __restrict__ edge_id,
                                                         const float* __restrict__ weight,
                                                         const uint8_t* __restrict__ keep,
                                                         const float* __restrict__ dinv, int64_t row_offset,
                                                         float* __restrict__ vals) {
-  const int row = (int)((blockIdx.x * 256u + threadIdx.x) >> 6);
-  if (row >= n_rows) return;
+  const int row = wave_row(row0, n_rows);
+  if (row < 0) return;
   const int lane = threadIdx.x & 63;
   const int s = indptr[row], e = indptr[row + 1];
   const float dr = dinv[row_offset + row];
@@ -72,15 +82,18 @@ extern "C" srh_status_t srh_adj_sym_normalize(int64_t n_rows, const int32_t* d_i
   SRH_REQUIRE(!d_keep || d_edge_id, "adj_sym_normalize: a keep mask needs edge ids");
   SRH_REQUIRE(row_offset >= 0 && phase >= 0 && phase <= 2, "adj_sym_normalize: bad row_offset / phase");
   hipStream_t st = srh::as_stream(stream);
-  const int blocks = (int)((n_rows + 3) / 4);
-  if (phase != 2) {
-    degree_kernel<<<blocks, 256, 0, st>>>((int)n_rows, d_indptr, d_edge_id, d_weight, d_keep,
-                                          d_inv_sqrt_table, d_inv_sqrt_table ? table_len : 0, d_deg_ws + row_offset);
+  // (every graph below 2^25 rows is one launch per kernel, as before; all degree launches precede the first normalize launch)
+  for (int64_t row0 = 0; phase != 2 && row0 < n_rows; row0 += kRowsPerLaunch) {
+    const int64_t rows = n_rows - row0 < kRowsPerLaunch ? n_rows - row0 : kRowsPerLaunch;
+    degree_kernel<<<(unsigned)((rows + 3) / 4), 256, 0, st>>>(row0, (int)n_rows, d_indptr, d_edge_id, d_weight, d_keep,
+                                                              d_inv_sqrt_table, d_inv_sqrt_table ? table_len : 0,
+                                                              d_deg_ws + row_offset);
     SRH_LAUNCH_CHECK();
   }
-  if (phase != 1) {
-    normalize_kernel<<<blocks, 256, 0, st>>>((int)n_rows, d_indptr, d_indices, d_edge_id, d_weight, d_keep, d_deg_ws,
-                                             row_offset, d_vals);
+  for (int64_t row0 = 0; phase != 1 && row0 < n_rows; row0 += kRowsPerLaunch) {
+    const int64_t rows = n_rows - row0 < kRowsPerLaunch ? n_rows - row0 : kRowsPerLaunch;
+    normalize_kernel<<<(unsigned)((rows + 3) / 4), 256, 0, st>>>(row0, (int)n_rows, d_indptr, d_indices, d_edge_id, d_weight,
+                                                                 d_keep, d_deg_ws, row_offset, d_vals);
     SRH_LAUNCH_CHECK();
   }
   return SRH_OK;
