@@ -19,6 +19,15 @@ void set_error(const char* fmt, ...);
     }                                             \
   } while (0)
 
+// a well-formed call for a shape the kernels do not cover
+#define SRH_SUPPORTED(cond, ...)                  \
+  do {                                            \
+    if (!(cond)) {                                \
+      ::srh::set_error(__VA_ARGS__);              \
+      return SRH_ERR_UNSUPPORTED;                 \
+    }                                             \
+  } while (0)
+
 #define SRH_HIP(call)                                                              \
   do {                                                                             \
     hipError_t e_ = (call);                                                        \
@@ -36,8 +45,49 @@ inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s);
 
 constexpr int kWave = 64;  // gfx950 wavefront
 
+constexpr int64_t ceil_div(int64_t n, int64_t per) { return (n + per - 1) / per; }
+
 // workspace carving: every array starts on a 256-byte boundary
 inline int64_t align256(int64_t b) { return (b + 255) & ~int64_t(255); }
+
+// One layout function per kernel family names its workspace arrays ONCE, in order, through a Carver: run on a null
+// base it only counts (`used` is what the family's *_ws_bytes entry point returns), run on the workspace it hands out
+// the pointers.  The size Python allocates and the addresses the kernels write cannot drift apart.
+struct Carver {
+  char* base;
+  int64_t used = 0;
+  explicit Carver(void* ws) : base(static_cast<char*>(ws)) {}
+  template <typename T>
+  void take(T*& p, int64_t count) {
+    p = base ? reinterpret_cast<T*>(base + used) : nullptr;
+    used += align256((int64_t)sizeof(T) * count);
+  }
+};
+
+// ---- chunk-ordered reductions over rows (chunked.hip): no float atomics, the same bits on every call ------------------
+// part[z * mats + m][e] = sum over rows r of chunk z (`chunk` rows each), ascending, of x[m][r][e]   (x: mats x n x len)
+srh_status_t colsum_chunks(const float* x, int64_t n, int64_t len, int mats, int chunk, float* part, hipStream_t st);
+// out[e] = scale * sum over z, ascending, of part[z][e]
+srh_status_t reduce_chunks(const float* part, int64_t chunks, int64_t len, float scale, float* out, hipStream_t st);
+
+// C (M x N) = A (M x K) B (K x N) with element strides, K cut into chunks of kchunk rows: chunk z takes rows
+// [z kchunk, (z + 1) kchunk) of K and writes its own slab C + z c_zstride (a weight gradient's partials per row chunk,
+// summed afterwards by reduce_chunks).
+enum GemmEpi { EPI_STORE = 0, EPI_RELU = 1, EPI_MASK = 2 };
+struct GemmArgs {
+  const float* A;
+  int64_t sam, sak;
+  const float* B;
+  int64_t sbk, sbn;
+  float* C;
+  int64_t ldc, c_zstride;
+  int64_t M, N, K, kchunk;
+  const float* aux;      // EPI_RELU: C *= (aux[m ldc + n] > 0)
+  const uint8_t* mask;   // EPI_MASK: rows m >= mask_row0: C *= mask[(m - mask_row0) N + n] ? mask_scale : 0
+  int64_t mask_row0;
+  float mask_scale;
+};
+srh_status_t gemm64(const GemmArgs& a, GemmEpi epi, int64_t chunks, hipStream_t st);
 
 // lanes per embedding row when each lane owns one float4 of it
 inline bool dim_supported(int d) { return d == 32 || d == 64 || d == 128 || d == 256; }

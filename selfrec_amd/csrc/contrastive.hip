@@ -24,7 +24,8 @@
 // the loss (the SOFTMAX template flag); everything else is data.  All four products run on v_mfma_f32_16x16x4_f32.  Every
 // output element is produced by one lane in a fixed order, so a call returns the same bits every time.
 //
-// Both passes are one kernel: a workgroup holds 64 "R" rows (16 per wave) in registers and streams "C" rows through LDS.
+// Both passes are one kernel on the row tile of rowtile.h: a workgroup holds 64 "R" rows (16 per wave) in registers and
+// streams "C" rows through LDS.
 //   S^T[c][r] = Cn_c . Rn_r                       (MFMA 1: A = C tile from LDS, B = R rows from registers)
 //   W[c][r]   = weight(S^T[c][r])                 (on the accumulator, in place)
 //   O^T[:, r] += sum_c Cn_c W[c][r]               (MFMA 2: the accumulator of MFMA 1 is its B operand, no lane movement;
@@ -42,15 +43,14 @@
 #include <algorithm>
 #include <cmath>
 
-#include "common.h"
+#include "rowtile.h"
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+using namespace srh;
 
-constexpr int kCtWaves = 4;                 // waves per workgroup; each owns 16 R rows
-constexpr int kCtRows = 16 * kCtWaves;      // R rows per workgroup
-constexpr int kCtCTile = 64;                // C rows staged in LDS per iteration
+constexpr int kCtRows = kRtRows;            // R rows per workgroup (16 per wave)
+constexpr int kCtCTile = kRtRows;           // C rows staged in LDS per iteration
 constexpr int kCtMaxProblems = 2;
 constexpr int kCtPass1Target = 512;         // pass-1 workgroups aimed for per problem (query tiles x key chunks)
 constexpr float kNormEps = 1e-12f;
@@ -99,28 +99,26 @@ inline int64_t ct_chunk_len(int64_t B, int64_t N) {
   return (per + kCtCTile - 1) / kCtCTile * kCtCTile;
 }
 
-using srh::align256;
-
-inline int64_t ct_ws_bytes(int64_t B, int64_t N, int D) {
-  const int64_t c = ct_chunks(B, N);
-  return align256(4 * B * D) + align256(4 * B) + align256(4 * N * D) + align256(4 * N) + align256(4 * c * B * D) +
-         align256(8 * c * B) + 2 * align256(4 * B) + align256(8 * B);
-}
-
-void ct_carve(CtProblem& p, char* ws, int D) {
-  char* cur = ws;
-  auto take = [&](int64_t bytes) { char* r = cur; cur += align256(bytes); return r; };
+// the workspace of a problem of (p.B, p.N): null ws measures, a workspace carves; returns the bytes
+int64_t ct_layout(CtProblem& p, void* ws, int D) {
+  Carver w(ws);
   p.chunks = ct_chunks(p.B, p.N);
   p.chunk_len = ct_chunk_len(p.B, p.N);
-  p.qn = (float*)take(4 * p.B * D);
-  p.qnorm = (float*)take(4 * p.B);
-  p.tn = (float*)take(4 * p.N * D);
-  p.tnorm = (float*)take(4 * p.N);
-  p.part_o = (float*)take(4 * p.chunks * p.B * D);
-  p.part_rs = (double*)take(8 * p.chunks * p.B);
-  p.cw = (float*)take(4 * p.B);
-  p.cd = (float*)take(4 * p.B);
-  p.row_loss = (double*)take(8 * p.B);
+  w.take(p.qn, p.B * D);
+  w.take(p.qnorm, p.B);
+  w.take(p.tn, p.N * D);
+  w.take(p.tnorm, p.N);
+  w.take(p.part_o, p.chunks * p.B * D);
+  w.take(p.part_rs, p.chunks * p.B);
+  w.take(p.cw, p.B);
+  w.take(p.cd, p.B);
+  w.take(p.row_loss, p.B);
+  return w.used;
+}
+inline int64_t ct_ws_bytes(int64_t B, int64_t N, int D) {
+  CtProblem p{};
+  p.B = B; p.N = N;
+  return ct_layout(p, nullptr, D);
 }
 
 // d(normalize(x))/dx applied to g: (g - y (y.g)) / |x| where |x| >= eps, g / eps below it (F.normalize's clamp_min)
@@ -163,8 +161,7 @@ __global__ __launch_bounds__(256) void ct_prep(CtArgs a) {
 // ---- the two passes (SOFTMAX: pass 2's positive-term rounding only) -------------------------------------------------
 template <int D, bool PASS2, bool SOFTMAX>
 __global__ __launch_bounds__(256) void ct_pass(CtArgs a) {
-  constexpr int LDS_STRIDE = D + 4;  // rows 4 floats apart in bank space: both LDS read patterns are conflict-free
-  __shared__ float cs[kCtCTile * LDS_STRIDE];
+  __shared__ float cs[kCtCTile * kRtStride<D>];
   __shared__ float cw[kCtCTile];
   __shared__ float cd[kCtCTile];
   __shared__ int32_t cid[kCtCTile];
@@ -181,27 +178,22 @@ __global__ __launch_bounds__(256) void ct_pass(CtArgs a) {
     cbeg = chunk * P.chunk_len;
     cend = cbeg + P.chunk_len < P.N ? cbeg + P.chunk_len : P.N;
   }
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, g = lane >> 4, j16 = lane & 15;
-  const int64_t r = rtile * kCtRows + wave * 16 + j16;
+  const RtLane L = rt_lane();
+  const int g = L.g, j16 = L.j16;
+  const int64_t r = rtile * kCtRows + L.wave * 16 + j16;
   const bool rok = r < nR;
   const float inv_tau = a.inv_tau;
 
-  float rf[D / 4];  // B operand of MFMA 1: Rn[r][4s + g]
+  float rf[D / 4];
 #pragma unroll
   for (int s = 0; s < D / 4; ++s) rf[s] = rok ? Rn[r * D + 4 * s + g] : 0.f;
   f32x4 o[D / 16];
-#pragma unroll
-  for (int b = 0; b < D / 16; ++b) o[b] = f32x4{0.f, 0.f, 0.f, 0.f};
+  zero_acc(o);
   double rs = 0.0;
 
   for (int64_t c0 = cbeg; c0 < cend; c0 += kCtCTile) {
     __syncthreads();
-    for (int e = threadIdx.x; e < kCtCTile * (D / 4); e += 256) {
-      const int i = e / (D / 4), v = e % (D / 4);
-      const int64_t c = c0 + i;
-      const float4 x = c < cend ? reinterpret_cast<const float4*>(Cn + c * D)[v] : srh::f4_zero();
-      *reinterpret_cast<float4*>(&cs[i * LDS_STRIDE + 4 * v]) = x;
-    }
+    stage_tile<D>(cs, Cn, c0, cend);
     if (threadIdx.x < kCtCTile) {
       const int64_t c = c0 + threadIdx.x;
       const bool cok = c < cend;
@@ -216,11 +208,7 @@ __global__ __launch_bounds__(256) void ct_pass(CtArgs a) {
     __syncthreads();
 #pragma unroll
     for (int sub = 0; sub < kCtCTile / 16; ++sub) {
-      f32x4 s = {0.f, 0.f, 0.f, 0.f};
-      const float* arow = &cs[(sub * 16 + j16) * LDS_STRIDE + g];
-#pragma unroll
-      for (int k = 0; k < D / 4; ++k) s = __builtin_amdgcn_mfma_f32_16x16x4f32(arow[4 * k], rf[k], s, 0, 0, 0);
-      // s[reg] = S^T[c = sub*16 + 4g + reg][r]
+      f32x4 s = score16<D>(cs, sub, j16, g, rf);
 #pragma unroll
       for (int reg = 0; reg < 4; ++reg) {
         const int ci = sub * 16 + 4 * g + reg;
@@ -235,53 +223,22 @@ __global__ __launch_bounds__(256) void ct_pass(CtArgs a) {
         }
         s[reg] = w;
       }
-#pragma unroll
-      for (int b = 0; b < D / 16; ++b) {
-#pragma unroll
-        for (int reg = 0; reg < 4; ++reg)
-          o[b] = __builtin_amdgcn_mfma_f32_16x16x4f32(cs[(sub * 16 + 4 * g + reg) * LDS_STRIDE + 16 * b + j16], s[reg], o[b],
-                                                      0, 0, 0);
-      }
+      accum16<D>(o, cs, sub, j16, g, s);
     }
   }
-  // o[b][reg] = O[r][16b + 4g + reg]
   if (!PASS2) {
-    rs += __shfl_xor(rs, 16);
-    rs += __shfl_xor(rs, 32);
+    rs = sum4(rs);
     if (!rok) return;
     const int64_t row = chunk * P.B + r;
     if (g == 0) P.part_rs[row] = rs;
-#pragma unroll
-    for (int b = 0; b < D / 16; ++b)
-      reinterpret_cast<float4*>(P.part_o + row * D + 16 * b + 4 * g)[0] = make_float4(o[b][0], o[b][1], o[b][2], o[b][3]);
+    store_acc<D>(o, P.part_o, row, g);
   } else {
     // dL/dt_j = gscale * O_j; then the normalisation backward of row j
     const float k = P.gscale;
-    float4 tv[D / 16];
-    float dot = 0.f;
 #pragma unroll
-    for (int b = 0; b < D / 16; ++b) {
-      tv[b] = rok ? reinterpret_cast<const float4*>(P.tn + r * D + 16 * b + 4 * g)[0] : srh::f4_zero();
-      o[b] *= k;
-      dot = fmaf(tv[b].x, o[b][0], fmaf(tv[b].y, o[b][1], fmaf(tv[b].z, o[b][2], fmaf(tv[b].w, o[b][3], dot))));
-    }
-    dot += __shfl_xor(dot, 16);
-    dot += __shfl_xor(dot, 32);
-    if (!rok) return;
-    const float nrm = P.tnorm[r];
-    const float inv = norm_bwd_scale(nrm);
-    const bool clamped = !(nrm > kNormEps);
-#pragma unroll
-    for (int b = 0; b < D / 16; ++b) {
-      float4 out;
-      if (clamped) {
-        out = make_float4(o[b][0] * inv, o[b][1] * inv, o[b][2] * inv, o[b][3] * inv);
-      } else {
-        out = make_float4((o[b][0] - tv[b].x * dot) * inv, (o[b][1] - tv[b].y * dot) * inv,
-                          (o[b][2] - tv[b].z * dot) * inv, (o[b][3] - tv[b].w * dot) * inv);
-      }
-      reinterpret_cast<float4*>(P.gt + r * D + 16 * b + 4 * g)[0] = out;
-    }
+    for (int b = 0; b < D / 16; ++b) o[b] *= k;
+    const float nrm = rok ? P.tnorm[r] : 1.f;
+    norm_bwd_store<D>(o, P.tn, norm_bwd_scale(nrm), !(nrm > kNormEps), r, rok, g, P.gt);
   }
 }
 
@@ -339,17 +296,9 @@ __global__ __launch_bounds__(256) void ct_finish(CtArgs a) {
 // ---- the loss: per-query terms summed in a fixed order, one workgroup per problem; scale s, or the mean ------------
 template <bool SOFTMAX>
 __global__ __launch_bounds__(256) void ct_loss(CtArgs a) {
-  __shared__ double part[256];
   const CtProblem& P = a.p[blockIdx.x];
-  double s = 0.0;
-  for (int64_t b = threadIdx.x; b < P.B; b += 256) s += P.row_loss[b];
-  part[threadIdx.x] = s;
-  __syncthreads();
-  for (int w = 128; w > 0; w >>= 1) {
-    if ((int)threadIdx.x < w) part[threadIdx.x] += part[threadIdx.x + w];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) P.loss[0] = SOFTMAX ? part[0] / (double)P.B : (double)P.scale * part[0];
+  const double s = block_sum_d(P.row_loss, P.B);
+  if (threadIdx.x == 0) P.loss[0] = SOFTMAX ? s / (double)P.B : (double)P.scale * s;
 }
 
 template <int D, bool SOFTMAX>
@@ -378,14 +327,6 @@ srh_status_t launch_ct(CtArgs& a, int np, hipStream_t st) {
 }
 
 // ---- softmax cross-entropy of M rows against the whole table: unbounded logits, running max --------------------------
-#define SRH_SUPPORTED(cond, ...)         \
-  do {                                   \
-    if (!(cond)) {                       \
-      ::srh::set_error(__VA_ARGS__);     \
-      return SRH_ERR_UNSUPPORTED;        \
-    }                                    \
-  } while (0)
-
 struct CeArgs {
   const float* h;        // M x D
   const float* t;        // N x D
@@ -404,21 +345,21 @@ struct CeArgs {
   int64_t chunks, chunk_len;
 };
 
-inline int64_t ce_ws_bytes(int64_t M, int64_t N, int D) {
-  const int64_t c = ct_chunks(M, N);
-  return align256(4 * c * M * D) + align256(8 * c * M) + align256(4 * c * M) + align256(4 * M) + align256(8 * M);
-}
-
-void ce_carve(CeArgs& a, char* ws, int D) {
-  char* cur = ws;
-  auto take = [&](int64_t bytes) { char* r = cur; cur += align256(bytes); return r; };
+int64_t ce_layout(CeArgs& a, void* ws, int D) {
+  Carver w(ws);
   a.chunks = ct_chunks(a.M, a.N);
   a.chunk_len = ct_chunk_len(a.M, a.N);
-  a.part_o = (float*)take(4 * a.chunks * a.M * D);
-  a.part_rs = (double*)take(8 * a.chunks * a.M);
-  a.part_m = (float*)take(4 * a.chunks * a.M);
-  a.lse = (float*)take(4 * a.M);
-  a.row_loss = (double*)take(8 * a.M);
+  w.take(a.part_o, a.chunks * a.M * D);
+  w.take(a.part_rs, a.chunks * a.M);
+  w.take(a.part_m, a.chunks * a.M);
+  w.take(a.lse, a.M);
+  w.take(a.row_loss, a.M);
+  return w.used;
+}
+inline int64_t ce_ws_bytes(int64_t M, int64_t N, int D) {
+  CeArgs a{};
+  a.M = M; a.N = N;
+  return ce_layout(a, nullptr, D);
 }
 
 // max over the four lanes (lane >> 4 = 0..3) that share an R row: the same bits in all four
@@ -432,8 +373,7 @@ __device__ __forceinline__ float ce_row_max4(float v) {
 // pass 2: R = the rows of T, C = all rows of H,    W = exp(s - lse_c) - [label_c == r]  -> dL/dT_r / scale
 template <int D, bool PASS2>
 __global__ __launch_bounds__(256) void ce_pass(CeArgs P) {
-  constexpr int LDS_STRIDE = D + 4;
-  __shared__ float cs[kCtCTile * LDS_STRIDE];
+  __shared__ float cs[kCtCTile * kRtStride<D>];
   __shared__ float clse[kCtCTile];
   __shared__ int32_t clab[kCtCTile];
   const int64_t nR = PASS2 ? P.N : P.M;
@@ -446,34 +386,26 @@ __global__ __launch_bounds__(256) void ce_pass(CeArgs P) {
     cbeg = chunk * P.chunk_len;
     cend = cbeg + P.chunk_len < P.N ? cbeg + P.chunk_len : P.N;
   }
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, g = lane >> 4, j16 = lane & 15;
-  const int64_t r = rtile * kCtRows + wave * 16 + j16;
+  const RtLane L = rt_lane();
+  const int g = L.g, j16 = L.j16;
+  const int64_t r = rtile * kCtRows + L.wave * 16 + j16;
   const bool rok = r < nR;
 
-  float rf[D / 4];  // B operand of MFMA 1: R[r][4s + g]
+  float rf[D / 4];
 #pragma unroll
   for (int s = 0; s < D / 4; ++s) rf[s] = rok ? Rn[r * D + 4 * s + g] : 0.f;
   f32x4 o[D / 16];
-#pragma unroll
-  for (int b = 0; b < D / 16; ++b) o[b] = f32x4{0.f, 0.f, 0.f, 0.f};
+  zero_acc(o);
   // pass 2 sums every 64-row tile from zero and adds the tile's sum here: a key that many rows name builds up a sum of
   // -H_m thousands of times the size of the P_mj H_m terms of all other rows, which a single running sum would then drop
   f32x4 tot[PASS2 ? D / 16 : 1];
-  if (PASS2) {
-#pragma unroll
-    for (int b = 0; b < D / 16; ++b) tot[b] = f32x4{0.f, 0.f, 0.f, 0.f};
-  }
+  if (PASS2) zero_acc(tot);
   double rs = 0.0;
   float m = -INFINITY;
 
   for (int64_t c0 = cbeg; c0 < cend; c0 += kCtCTile) {
     __syncthreads();
-    for (int e = threadIdx.x; e < kCtCTile * (D / 4); e += 256) {
-      const int i = e / (D / 4), v = e % (D / 4);
-      const int64_t c = c0 + i;
-      const float4 x = c < cend ? reinterpret_cast<const float4*>(Cn + c * D)[v] : srh::f4_zero();
-      *reinterpret_cast<float4*>(&cs[i * LDS_STRIDE + 4 * v]) = x;
-    }
+    stage_tile<D>(cs, Cn, c0, cend);
     if (PASS2 && threadIdx.x < kCtCTile) {
       const int64_t c = c0 + threadIdx.x;
       clse[threadIdx.x] = c < cend ? P.lse[c] : INFINITY;      // (a row past M weighs exp(-inf) = 0)
@@ -482,13 +414,7 @@ __global__ __launch_bounds__(256) void ce_pass(CeArgs P) {
     __syncthreads();
     f32x4 s[kCtCTile / 16];
 #pragma unroll
-    for (int sub = 0; sub < kCtCTile / 16; ++sub) {
-      f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-      const float* arow = &cs[(sub * 16 + j16) * LDS_STRIDE + g];
-#pragma unroll
-      for (int k = 0; k < D / 4; ++k) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(arow[4 * k], rf[k], acc, 0, 0, 0);
-      s[sub] = acc;  // s[sub][reg] = S^T[c = sub*16 + 4g + reg][r]
-    }
+    for (int sub = 0; sub < kCtCTile / 16; ++sub) s[sub] = score16<D>(cs, sub, j16, g, rf);
     if (!PASS2) {
       // the keys past the chunk's end are -inf before the max; a tile holds at least one key, so the max is finite
       float mx = -INFINITY;
@@ -525,45 +451,32 @@ __global__ __launch_bounds__(256) void ce_pass(CeArgs P) {
         }
     }
 #pragma unroll
-    for (int sub = 0; sub < kCtCTile / 16; ++sub)
-#pragma unroll
-      for (int b = 0; b < D / 16; ++b)
-#pragma unroll
-        for (int reg = 0; reg < 4; ++reg)
-          o[b] = __builtin_amdgcn_mfma_f32_16x16x4f32(cs[(sub * 16 + 4 * g + reg) * LDS_STRIDE + 16 * b + j16], s[sub][reg],
-                                                      o[b], 0, 0, 0);
+    for (int sub = 0; sub < kCtCTile / 16; ++sub) accum16<D>(o, cs, sub, j16, g, s[sub]);
     if (PASS2) {
 #pragma unroll
-      for (int b = 0; b < D / 16; ++b) {
-        tot[b] += o[b];
-        o[b] = f32x4{0.f, 0.f, 0.f, 0.f};
-      }
+      for (int b = 0; b < D / 16; ++b) tot[b] += o[b];
+      zero_acc(o);
     }
   }
   if (PASS2) {
 #pragma unroll
     for (int b = 0; b < D / 16; ++b) o[b] = tot[b];
   }
-  // o[b][reg] = O[r][16b + 4g + reg]
   if (!PASS2) {
-    rs += __shfl_xor(rs, 16);
-    rs += __shfl_xor(rs, 32);
+    rs = sum4(rs);
     if (!rok) return;
     const int64_t row = chunk * P.M + r;
     if (g == 0) {
       P.part_rs[row] = rs;
       P.part_m[row] = m;
     }
-#pragma unroll
-    for (int b = 0; b < D / 16; ++b)
-      reinterpret_cast<float4*>(P.part_o + row * D + 16 * b + 4 * g)[0] = make_float4(o[b][0], o[b][1], o[b][2], o[b][3]);
+    store_acc<D>(o, P.part_o, row, g);
   } else {
     if (!rok) return;
     const float k = P.scale;
 #pragma unroll
-    for (int b = 0; b < D / 16; ++b)
-      reinterpret_cast<float4*>(P.gt + r * D + 16 * b + 4 * g)[0] =
-          make_float4(k * o[b][0], k * o[b][1], k * o[b][2], k * o[b][3]);
+    for (int b = 0; b < D / 16; ++b) o[b] *= k;
+    store_acc<D>(o, P.gt, r, g);
   }
 }
 
@@ -602,16 +515,8 @@ __global__ __launch_bounds__(256) void ce_finish(CeArgs P) {
 
 // the loss: the row terms summed in a fixed order by one workgroup, times the scale
 __global__ __launch_bounds__(256) void ce_loss(CeArgs P) {
-  __shared__ double part[256];
-  double s = 0.0;
-  for (int64_t b = threadIdx.x; b < P.M; b += 256) s += P.row_loss[b];
-  part[threadIdx.x] = s;
-  __syncthreads();
-  for (int w = 128; w > 0; w >>= 1) {
-    if ((int)threadIdx.x < w) part[threadIdx.x] += part[threadIdx.x + w];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) P.loss[0] = (double)P.scale * part[0];
+  const double s = block_sum_d(P.row_loss, P.M);
+  if (threadIdx.x == 0) P.loss[0] = (double)P.scale * s;
 }
 
 template <int D>
@@ -657,8 +562,7 @@ srh_status_t srh_table_nce_fwd_bwd(const srh_table_nce_problem_t* problems, int3
     p.q = s.d_q; p.t = s.d_t; p.idx = s.d_idx; p.B = s.B; p.N = s.N; p.scale = s.loss_scale;
     p.gscale = s.loss_scale * a.inv_tau;
     p.loss = s.d_loss; p.gq = s.d_gq; p.gt = s.d_gt;
-    ct_carve(p, ws, d);
-    ws += ct_ws_bytes(s.B, s.N, d);
+    ws += ct_layout(p, ws, d);
   }
   hipStream_t st = srh::as_stream(stream);
   return d == 64 ? launch_ct<64, false>(a, n_problems, st) : launch_ct<128, false>(a, n_problems, st);
@@ -681,7 +585,7 @@ srh_status_t srh_batch_softmax_fwd_bwd(const float* d_u, const float* d_v, int64
   p.q = d_u; p.t = d_v; p.idx = nullptr; p.B = B; p.N = B;
   p.gscale = a.inv_tau / (float)B;
   p.loss = d_loss; p.gq = d_gu; p.gt = d_gv;
-  ct_carve(p, static_cast<char*>(d_ws), d);
+  ct_layout(p, d_ws, d);
   hipStream_t st = srh::as_stream(stream);
   return d == 64 ? launch_ct<64, true>(a, 1, st) : launch_ct<128, true>(a, 1, st);
 }
@@ -701,7 +605,7 @@ srh_status_t srh_table_ce_fwd_bwd(const float* d_h, int64_t M, const float* d_t,
   CeArgs a{};
   a.h = d_h; a.t = d_t; a.label = d_labels; a.M = M; a.N = N; a.scale = loss_scale;
   a.loss = d_loss; a.gh = d_gh; a.gt = d_gt;
-  ce_carve(a, static_cast<char*>(d_ws), d);
+  ce_layout(a, d_ws, d);
   hipStream_t st = srh::as_stream(stream);
   return d == 64 ? launch_ce<64>(a, st) : launch_ce<128>(a, st);
 }

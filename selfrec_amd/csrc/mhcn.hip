@@ -1,6 +1,6 @@
 // MHCN (model/graph/MHCN.py of the reference): the three pieces of its step that no other kernel here serves.
 // DESIGN.md 4.21.  All arithmetic fp32, losses leave as float64, no float atomics: every reduction over rows runs in fixed
-// chunks whose partials are summed in chunk order (ssl4rec.hip's scheme), so a call returns the same bits every time.
+// chunks whose partials are summed in chunk order (chunked.hip), so a call returns the same bits every time.
 //
 // Gate (self_gating / self_supervised_gating, MHCN.py:79-83):  Y_c = X (.) sigmoid(X W_c + b_c), c < C <= 4, X (n x D),
 //   W_c (D x D, the x @ W layout), b_c (D).
@@ -13,36 +13,24 @@
 //              dX^T += W_c dZ_c^T from the SAME staged chunk (the accumulator layout is the B layout with the k order
 //              4 * (lane >> 4) + reg); dY_c (.) S_c lands on the accumulator element of the same (row, column).
 //   gate_wgrad dW_c = X^T dZ_c per chunk of kRowChunk rows on the MFMA; db_c the column sums per chunk; both summed in
-//              chunk order.
+//              chunk order (chunked.hip).
 // Channel mix (channel_attention, MHCN.py:85-93): w_c[r] = E_c[r] . q, s[r] = softmax_c w_c[r],
 //   out[r] = sum_c s_c[r] E_c[r] + beta X[r].  One wave per row, forward and backward; dq is a chunk-ordered reduction.
 // MIM (hierarchical_self_supervision, MHCN.py:159-181), forward and backward in one call: see srh_mim_fwd_bwd below.
 #include <algorithm>
 #include <cmath>
 
-#include "common.h"
+#include "rowtile.h"
 
 namespace {
 
 using namespace srh;
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kMaxGates = 4;
 constexpr int kJc = 64;                 // output columns per staged weight chunk
 constexpr int kLds = kJc + 4;           // LDS row stride (floats) of the staged chunk
 constexpr int kRowChunk = 256;          // rows per partial of the gate's weight-gradient reductions
 constexpr int kMixChunk = 64;           // rows per partial of the mix / MIM reductions (16 per wave, ascending)
-
-#define SRH_SUPPORTED(cond, ...)         \
-  do {                                   \
-    if (!(cond)) {                       \
-      ::srh::set_error(__VA_ARGS__);     \
-      return SRH_ERR_UNSUPPORTED;        \
-    }                                    \
-  } while (0)
-
-inline int64_t chunks_of(int64_t n, int64_t per) { return (n + per - 1) / per; }
 
 __device__ __forceinline__ float sigmoidf_(float x) { return 1.f / (1.f + expf(-x)); }
 // softplus, finite for every finite x
@@ -146,7 +134,9 @@ __global__ __launch_bounds__(256) void gate_kernel(GateArgs a) {
 }
 
 // part[(z * C + c)][k][j] = sum over rows r of chunk z, ascending in steps of 16, of X[r][k] dZ_c[r][j]
-// grid (D / 64 column tiles, D / 64 row tiles, chunks * C); 64 x 64 tile per workgroup, 16 rows of it per wave
+// grid (D / 64 column tiles, D / 64 row tiles, chunks * C); 64 x 64 tile per workgroup, 16 rows of it per wave.  The staging
+// and MFMA order of chunked.hip's gemm64 with D at compile time and no bounds checks: that one measured 15 % slower on
+// the gate backward (profiles/NOTES_rowtile.md).
 template <int D>
 __global__ __launch_bounds__(256) void gate_wgrad(const float* __restrict__ x, const float* __restrict__ dz, int64_t n, int C,
                                                   float* __restrict__ part) {
@@ -190,63 +180,55 @@ __global__ __launch_bounds__(256) void gate_wgrad(const float* __restrict__ x, c
   }
 }
 
-// part[(z * mats + m)][e] = sum over rows r of chunk z (chunk rows each), ascending, of x[m][r][e]   (x: mats x n x len)
-__global__ __launch_bounds__(64) void colsum_part(const float* __restrict__ x, int64_t n, int len, int mats, int chunk,
-                                                  float* __restrict__ part) {
-  const int e = blockIdx.x * 64 + threadIdx.x;
-  const int64_t z = blockIdx.y / mats;
-  const int m = blockIdx.y % mats;
-  if (e >= len) return;
-  const float* xm = x + (int64_t)m * n * len;
-  const int64_t r1 = std::min<int64_t>((z + 1) * chunk, n);
-  float s = 0.f;
-  for (int64_t r = z * chunk; r < r1; ++r) s += xm[r * len + e];
-  part[(int64_t)blockIdx.y * len + e] = s;
-}
-
-// out[e] = scale * sum over z, ascending, of part[z][e]
-__global__ __launch_bounds__(256) void reduce_chunks(const float* __restrict__ part, int64_t chunks, int64_t len, float scale,
-                                                     float* __restrict__ out) {
-  const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (e >= len) return;
-  float s = 0.f;
-  for (int64_t z = 0; z < chunks; ++z) s += part[z * len + e];
-  out[e] = s * scale;
-}
-
-inline int64_t gate_bwd_ws(int64_t n, int D, int C) {
-  const int64_t z = chunks_of(n, kRowChunk);
-  return align256(4 * (int64_t)C * n * D) + align256(4 * z * C * D * D) + align256(4 * z * C * D);
+struct GateBwdWs {
+  float* dz;       // C x n x D
+  float* part_w;   // chunks x C x D x D
+  float* part_b;   // chunks x C x D
+};
+// null ws measures, a workspace carves; returns the bytes
+int64_t gate_bwd_layout(GateBwdWs& w, void* ws, int64_t n, int D, int C) {
+  Carver cv(ws);
+  const int64_t z = ceil_div(n, kRowChunk);
+  cv.take(w.dz, (int64_t)C * n * D);
+  cv.take(w.part_w, z * C * D * D);
+  cv.take(w.part_b, z * C * D);
+  return cv.used;
 }
 
 template <int D>
 srh_status_t launch_gate_fwd(const GateArgs& a, hipStream_t st) {
-  gate_kernel<D, false><<<(unsigned)chunks_of(a.n, 64), 256, 0, st>>>(a);
+  gate_kernel<D, false><<<(unsigned)ceil_div(a.n, 64), 256, 0, st>>>(a);
   SRH_LAUNCH_CHECK();
   return SRH_OK;
 }
 
 template <int D>
-srh_status_t launch_gate_bwd(GateArgs a, float* gw, float* gb, char* ws, hipStream_t st) {
-  const int64_t z = chunks_of(a.n, kRowChunk);
+srh_status_t launch_gate_bwd(GateArgs a, float* gw, float* gb, void* ws, hipStream_t st) {
+  const int64_t z = ceil_div(a.n, kRowChunk);
   const int C = a.C;
-  a.dz = (float*)ws;
-  float* part_w = (float*)(ws + align256(4 * (int64_t)C * a.n * D));
-  float* part_b = (float*)((char*)part_w + align256(4 * z * C * D * D));
-  gate_kernel<D, true><<<(unsigned)chunks_of(a.n, 64), 256, 0, st>>>(a);
+  GateBwdWs w;
+  gate_bwd_layout(w, ws, a.n, D, C);
+  a.dz = w.dz;
+  gate_kernel<D, true><<<(unsigned)ceil_div(a.n, 64), 256, 0, st>>>(a);
   SRH_LAUNCH_CHECK();
-  gate_wgrad<D><<<dim3(D / 64, D / 64, (unsigned)(z * C)), 256, 0, st>>>(a.x, a.dz, a.n, C, part_w);
+  gate_wgrad<D><<<dim3(D / 64, D / 64, (unsigned)(z * C)), 256, 0, st>>>(a.x, w.dz, a.n, C, w.part_w);
   SRH_LAUNCH_CHECK();
-  colsum_part<<<dim3(D / 64, (unsigned)(z * C)), 64, 0, st>>>(a.dz, a.n, D, C, kRowChunk, part_b);
-  SRH_LAUNCH_CHECK();
-  reduce_chunks<<<(unsigned)chunks_of((int64_t)C * D * D, 256), 256, 0, st>>>(part_w, z, (int64_t)C * D * D, 1.f, gw);
-  SRH_LAUNCH_CHECK();
-  reduce_chunks<<<(unsigned)chunks_of((int64_t)C * D, 256), 256, 0, st>>>(part_b, z, (int64_t)C * D, 1.f, gb);
-  SRH_LAUNCH_CHECK();
-  return SRH_OK;
+  srh_status_t s;
+  if ((s = colsum_chunks(w.dz, a.n, D, C, kRowChunk, w.part_b, st)) != SRH_OK) return s;
+  if ((s = reduce_chunks(w.part_w, z, (int64_t)C * D * D, 1.f, gw, st)) != SRH_OK) return s;
+  return reduce_chunks(w.part_b, z, (int64_t)C * D, 1.f, gb, st);
 }
 
 // ---- channel mix -------------------------------------------------------------------------------------------------------
+// wp[wave][e]: the four waves' partials of a chunk's D column sums, added in wave order into row blockIdx.x of part
+template <int D>
+__device__ __forceinline__ void wave_partials_store(const float* wp, float* __restrict__ part) {
+  if (threadIdx.x < D) {
+    const int e = threadIdx.x;
+    part[(int64_t)blockIdx.x * D + e] = ((wp[e] + wp[D + e]) + wp[2 * D + e]) + wp[3 * D + e];
+  }
+}
+
 struct MixArgs {
   const float* e[3];
   const float* q;
@@ -338,10 +320,7 @@ __global__ __launch_bounds__(256) void mix_bwd(MixArgs a) {
 #pragma unroll
   for (int k = 0; k < Q; ++k) wp[wave * D + lane + 64 * k] = dq[k];
   __syncthreads();
-  if (threadIdx.x < D) {
-    const int e = threadIdx.x;
-    a.part[(int64_t)blockIdx.x * D + e] = ((wp[e] + wp[D + e]) + wp[2 * D + e]) + wp[3 * D + e];
-  }
+  wave_partials_store<D>(wp, a.part);
 }
 
 // ---- MIM ---------------------------------------------------------------------------------------------------------------
@@ -366,23 +345,20 @@ struct MimArgs {
   int64_t chunks;
 };
 
-inline int64_t mim_ws(int64_t n, int D) {
-  const int64_t z = chunks_of(n, kMixChunk);
-  return 3 * align256(4 * n) + 2 * align256(4 * D) + align256(4 * 3 * n) + align256(4 * z * D) + 2 * align256(4 * D) +
-         align256(8 * z);
-}
-
-void mim_carve(MimArgs& a, char* ws, int D) {
-  char* cur = ws;
-  auto take = [&](int64_t bytes) { char* r = cur; cur += align256(bytes); return r; };
-  a.chunks = chunks_of(a.n, kMixChunk);
-  for (int i = 0; i < 3; ++i) a.ip[i] = (int32_t*)take(4 * a.n);
-  for (int i = 0; i < 2; ++i) a.ic[i] = (int32_t*)take(4 * D);
-  a.kk = (float*)take(4 * 3 * a.n);
-  a.gpart = (float*)take(4 * a.chunks * D);
-  a.g = (float*)take(4 * D);
-  a.dg = (float*)take(4 * D);
-  a.lpart = (double*)take(8 * a.chunks);
+// the workspace of a.n rows: null ws measures, a workspace carves; returns the bytes.  The ORDER of the first three
+// lines matters: launch_mim sets ip[0] .. kk to -1 with one memset, so the five inverse maps lie back to back with kk
+// right behind them.
+int64_t mim_layout(MimArgs& a, void* ws, int D) {
+  Carver w(ws);
+  a.chunks = ceil_div(a.n, kMixChunk);
+  for (int i = 0; i < 3; ++i) w.take(a.ip[i], a.n);
+  for (int i = 0; i < 2; ++i) w.take(a.ic[i], D);
+  w.take(a.kk, 3 * a.n);
+  w.take(a.gpart, a.chunks * D);
+  w.take(a.g, D);
+  w.take(a.dg, D);
+  w.take(a.lpart, a.chunks);
+  return w.used;
 }
 
 // the inverse permutations (the workspace holds -1 everywhere before); an entry outside its range is left out
@@ -466,10 +442,7 @@ __global__ __launch_bounds__(256) void mim_rows(MimArgs a) {
   for (int k = 0; k < Q; ++k) wp[wave * D + lane + 64 * k] = dgp[k];
   if (lane == 0) lp[wave] = lsum;
   __syncthreads();
-  if (threadIdx.x < D) {
-    const int e = threadIdx.x;
-    a.gpart[(int64_t)blockIdx.x * D + e] = ((wp[e] + wp[D + e]) + wp[2 * D + e]) + wp[3 * D + e];
-  }
+  wave_partials_store<D>(wp, a.gpart);
   if (threadIdx.x == 0) a.lpart[blockIdx.x] = ((lp[0] + lp[1]) + lp[2]) + lp[3];
 }
 
@@ -529,21 +502,20 @@ __global__ __launch_bounds__(256) void mim_grads(MimArgs a) {
 }
 
 template <int D>
-srh_status_t launch_mim(MimArgs& a, char* ws, hipStream_t st) {
-  mim_carve(a, ws, D);
+srh_status_t launch_mim(MimArgs& a, void* ws, hipStream_t st) {
+  mim_layout(a, ws, D);
   // the inverse maps start at -1
   SRH_HIP(hipMemsetAsync(a.ip[0], 0xFF, (size_t)((char*)a.kk - (char*)a.ip[0]), st));
-  mim_inverse<D><<<(unsigned)chunks_of(std::max<int64_t>(a.n, D), 256), 256, 0, st>>>(a);
+  mim_inverse<D><<<(unsigned)ceil_div(std::max<int64_t>(a.n, D), 256), 256, 0, st>>>(a);
   SRH_LAUNCH_CHECK();
-  colsum_part<<<dim3(D / 64, (unsigned)a.chunks), 64, 0, st>>>(a.edge, a.n, D, 1, kMixChunk, a.gpart);
-  SRH_LAUNCH_CHECK();
-  reduce_chunks<<<1, 256, 0, st>>>(a.gpart, a.chunks, D, a.inv_n, a.g);
-  SRH_LAUNCH_CHECK();
+  srh_status_t s;
+  if ((s = colsum_chunks(a.edge, a.n, D, 1, kMixChunk, a.gpart, st)) != SRH_OK) return s;
+  if ((s = reduce_chunks(a.gpart, a.chunks, D, a.inv_n, a.g, st)) != SRH_OK) return s;
   mim_rows<D><<<(unsigned)a.chunks, 256, 0, st>>>(a);
   SRH_LAUNCH_CHECK();
   mim_finish<D><<<1, 256, 0, st>>>(a);
   SRH_LAUNCH_CHECK();
-  mim_grads<D><<<(unsigned)chunks_of(a.n, 4), 256, 0, st>>>(a);
+  mim_grads<D><<<(unsigned)ceil_div(a.n, 4), 256, 0, st>>>(a);
   SRH_LAUNCH_CHECK();
   return SRH_OK;
 }
@@ -569,7 +541,8 @@ srh_status_t srh_gate_fwd_f32(const float* d_x, const float* d_w, const float* d
 
 int64_t srh_gate_bwd_ws_bytes(int64_t n, int32_t d, int32_t n_gates) {
   if (n <= 0 || bad_n(n) || (d != 64 && d != 128) || n_gates < 1 || n_gates > kMaxGates) return 0;
-  return gate_bwd_ws(n, d, n_gates);
+  GateBwdWs w;
+  return gate_bwd_layout(w, nullptr, n, d, n_gates);
 }
 
 srh_status_t srh_gate_bwd_f32(const float* d_x, const float* d_w, const float* d_b, const float* d_gy, int64_t n, int32_t d,
@@ -587,8 +560,7 @@ srh_status_t srh_gate_bwd_f32(const float* d_x, const float* d_w, const float* d
   SRH_REQUIRE(d_x && d_w && d_b && d_gy && d_gx && d_ws, "gate_bwd: null argument");
   GateArgs a{};
   a.x = d_x; a.w = d_w; a.b = d_b; a.n = n; a.C = n_gates; a.gy = d_gy; a.gx = d_gx;
-  return d == 64 ? launch_gate_bwd<64>(a, d_gw, d_gb, static_cast<char*>(d_ws), st)
-                 : launch_gate_bwd<128>(a, d_gw, d_gb, static_cast<char*>(d_ws), st);
+  return d == 64 ? launch_gate_bwd<64>(a, d_gw, d_gb, d_ws, st) : launch_gate_bwd<128>(a, d_gw, d_gb, d_ws, st);
 }
 
 srh_status_t srh_chan_mix_fwd_f32(const float* d_e1, const float* d_e2, const float* d_e3, const float* d_q,
@@ -602,15 +574,15 @@ srh_status_t srh_chan_mix_fwd_f32(const float* d_e1, const float* d_e2, const fl
   MixArgs a{};
   a.e[0] = d_e1; a.e[1] = d_e2; a.e[2] = d_e3; a.q = d_q; a.x = d_x; a.beta = beta; a.n = n; a.out = d_out; a.score = d_score;
   hipStream_t st = as_stream(stream);
-  if (d == 64) mix_fwd<64><<<(unsigned)chunks_of(n, 4), 256, 0, st>>>(a);
-  else mix_fwd<128><<<(unsigned)chunks_of(n, 4), 256, 0, st>>>(a);
+  if (d == 64) mix_fwd<64><<<(unsigned)ceil_div(n, 4), 256, 0, st>>>(a);
+  else mix_fwd<128><<<(unsigned)ceil_div(n, 4), 256, 0, st>>>(a);
   SRH_LAUNCH_CHECK();
   return SRH_OK;
 }
 
 int64_t srh_chan_mix_bwd_ws_bytes(int64_t n, int32_t d) {
   if (n <= 0 || bad_n(n) || (d != 64 && d != 128)) return 0;
-  return align256(4 * chunks_of(n, kMixChunk) * d);
+  return align256(4 * ceil_div(n, kMixChunk) * d);
 }
 
 srh_status_t srh_chan_mix_bwd_f32(const float* d_e1, const float* d_e2, const float* d_e3, const float* d_q,
@@ -630,18 +602,18 @@ srh_status_t srh_chan_mix_bwd_f32(const float* d_e1, const float* d_e2, const fl
   MixArgs a{};
   a.e[0] = d_e1; a.e[1] = d_e2; a.e[2] = d_e3; a.q = d_q; a.beta = beta; a.n = n; a.score = const_cast<float*>(d_score);
   a.gout = d_gout; a.ge[0] = d_ge1; a.ge[1] = d_ge2; a.ge[2] = d_ge3; a.gx = d_gx; a.part = static_cast<float*>(d_ws);
-  const int64_t z = chunks_of(n, kMixChunk);
+  const int64_t z = ceil_div(n, kMixChunk);
   if (d == 64) mix_bwd<64><<<(unsigned)z, 256, 0, st>>>(a);
   else mix_bwd<128><<<(unsigned)z, 256, 0, st>>>(a);
   SRH_LAUNCH_CHECK();
-  reduce_chunks<<<1, 256, 0, st>>>(a.part, z, d, 1.f, d_gq);
-  SRH_LAUNCH_CHECK();
-  return SRH_OK;
+  return reduce_chunks(a.part, z, d, 1.f, d_gq, st);
 }
 
 int64_t srh_mim_ws_bytes(int64_t n, int32_t d) {
   if (n <= 0 || bad_n(n) || (d != 64 && d != 128)) return 0;
-  return mim_ws(n, d);
+  MimArgs a{};
+  a.n = n;
+  return mim_layout(a, nullptr, d);
 }
 
 srh_status_t srh_mim_fwd_bwd(const srh_mim_args_t* args, void* d_ws, void* stream) {
@@ -668,7 +640,7 @@ srh_status_t srh_mim_fwd_bwd(const srh_mim_args_t* args, void* d_ws, void* strea
   }
   a.em = s.d_em; a.edge = s.d_edge; a.n = s.n; a.scale = s.loss_scale; a.inv_n = (float)(1.0 / (double)s.n);
   a.loss = s.d_loss; a.gem = s.d_gem; a.gedge = s.d_gedge;
-  return s.d == 64 ? launch_mim<64>(a, static_cast<char*>(d_ws), st) : launch_mim<128>(a, static_cast<char*>(d_ws), st);
+  return s.d == 64 ? launch_mim<64>(a, d_ws, st) : launch_mim<128>(a, d_ws, st);
 }
 
 }  // extern "C"

@@ -28,14 +28,6 @@ using namespace srh;
 constexpr int kInFlight = 4;            // iterations (of 64 / G candidates) whose loads are issued before the first use
 constexpr int kScanUnroll = 4;          // 64-key strides of the leader test between two early-exit votes
 
-#define SRH_SUPPORTED(cond, ...)         \
-  do {                                   \
-    if (!(cond)) {                       \
-      ::srh::set_error(__VA_ARGS__);     \
-      return SRH_ERR_UNSUPPORTED;        \
-    }                                    \
-  } while (0)
-
 struct MixupArgs {
   const float* table[SRH_MIXUP_MAX_HOPS];
   const float* alpha[SRH_MIXUP_MAX_HOPS];     // all NULL: drawn

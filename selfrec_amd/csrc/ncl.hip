@@ -6,24 +6,25 @@
 //   update  stable counting sort of the rows by cluster, then each cluster sums its rows in ascending row order
 #include <cmath>
 
-#include "common.h"
+#include "rowtile.h"
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+using namespace srh;
 
-constexpr int kKmRows = 64;    // rows per assign workgroup (16 per wave)
-constexpr int kKmCTile = 64;   // centroids staged in LDS per iteration
+constexpr int kKmRows = kRtRows;    // rows per assign workgroup (16 per wave)
+constexpr int kKmCTile = kRtRows;   // centroids staged in LDS per iteration
 
 // ---- k-means assign ------------------------------------------------------------------------------------------------
 template <int D>
 __global__ __launch_bounds__(256) void km_assign(const float* __restrict__ x, int64_t n, const float* __restrict__ c,
                                                  int64_t k, int32_t* __restrict__ out_ids, float* __restrict__ out_dist) {
-  constexpr int LDS_STRIDE = D + 4;
+  constexpr int LDS_STRIDE = kRtStride<D>;
   __shared__ float cs[kKmCTile * LDS_STRIDE];
   __shared__ float cn2[kKmCTile];
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, g = lane >> 4, j16 = lane & 15;
-  const int64_t r = (int64_t)blockIdx.x * kKmRows + wave * 16 + j16;
+  const RtLane L = rt_lane();
+  const int g = L.g, j16 = L.j16;
+  const int64_t r = (int64_t)blockIdx.x * kKmRows + L.wave * 16 + j16;
   const bool rok = r < n;
   float rf[D / 4];
   float xx = 0.f;
@@ -32,18 +33,12 @@ __global__ __launch_bounds__(256) void km_assign(const float* __restrict__ x, in
     rf[s] = rok ? x[r * D + 4 * s + g] : 0.f;
     xx = fmaf(rf[s], rf[s], xx);
   }
-  xx += __shfl_xor(xx, 16);
-  xx += __shfl_xor(xx, 32);
+  xx = sum4(xx);
   float best = INFINITY;
   int32_t best_j = 0x7fffffff;
   for (int64_t c0 = 0; c0 < k; c0 += kKmCTile) {
     __syncthreads();
-    for (int e = threadIdx.x; e < kKmCTile * (D / 4); e += 256) {
-      const int i = e / (D / 4), v = e % (D / 4);
-      const int64_t cj = c0 + i;
-      const float4 y = cj < k ? reinterpret_cast<const float4*>(c + cj * D)[v] : srh::f4_zero();
-      *reinterpret_cast<float4*>(&cs[i * LDS_STRIDE + 4 * v]) = y;
-    }
+    stage_tile<D>(cs, c, c0, k);
     __syncthreads();
     if (threadIdx.x < kKmCTile) {
       float s2 = 0.f;
@@ -53,10 +48,7 @@ __global__ __launch_bounds__(256) void km_assign(const float* __restrict__ x, in
     __syncthreads();
 #pragma unroll
     for (int sub = 0; sub < kKmCTile / 16; ++sub) {
-      f32x4 s = {0.f, 0.f, 0.f, 0.f};
-      const float* arow = &cs[(sub * 16 + j16) * LDS_STRIDE + g];
-#pragma unroll
-      for (int q = 0; q < D / 4; ++q) s = __builtin_amdgcn_mfma_f32_16x16x4f32(arow[4 * q], rf[q], s, 0, 0, 0);
+      const f32x4 s = score16<D>(cs, sub, j16, g, rf);
       // this lane's centroids come in ascending j: a strict < keeps the lowest j of equal distances
 #pragma unroll
       for (int reg = 0; reg < 4; ++reg) {
@@ -94,23 +86,16 @@ struct KmWs {
   int32_t* order;      // n: row ids sorted by cluster, ascending within a cluster
 };
 
-__host__ __device__ inline int64_t km_chunks(int64_t n) { return (n + kKmChunk - 1) / kKmChunk; }
+constexpr int64_t km_chunks(int64_t n) { return ceil_div(n, kKmChunk); }
 
-using srh::align256;
-
-inline int64_t km_ws_bytes(int64_t n, int64_t k) {
-  return align256(4 * km_chunks(n) * k) + align256(4 * n) + align256(4 * k) + align256(4 * n);
-}
-
-KmWs km_carve(char* ws, int64_t n, int64_t k) {
-  KmWs w;
-  char* cur = ws;
-  auto take = [&](int64_t bytes) { char* r = cur; cur += align256(bytes); return r; };
-  w.chunk_cnt = (int32_t*)take(4 * km_chunks(n) * k);
-  w.rank = (int32_t*)take(4 * n);
-  w.start = (int32_t*)take(4 * k);
-  w.order = (int32_t*)take(4 * n);
-  return w;
+// null ws measures, a workspace carves; returns the bytes
+int64_t km_layout(KmWs& w, void* ws, int64_t n, int64_t k) {
+  Carver c(ws);
+  c.take(w.chunk_cnt, km_chunks(n) * k);
+  c.take(w.rank, n);
+  c.take(w.start, k);
+  c.take(w.order, n);
+  return c.used;
 }
 
 __device__ __forceinline__ bool km_valid(int32_t id, int64_t k) { return id >= 0 && (int64_t)id < k; }
@@ -218,7 +203,8 @@ srh_status_t srh_kmeans_assign_f32(const float* d_x, int64_t n, const float* d_c
 
 int64_t srh_kmeans_update_ws_bytes(int64_t n, int64_t k) {
   if (n <= 0 || k <= 0) return 0;
-  return km_ws_bytes(n, k);
+  KmWs w;
+  return km_layout(w, nullptr, n, k);
 }
 
 srh_status_t srh_kmeans_update_f32(const float* d_x, int64_t n, const int32_t* d_ids, int64_t k, int32_t d,
@@ -226,7 +212,8 @@ srh_status_t srh_kmeans_update_f32(const float* d_x, int64_t n, const int32_t* d
   SRH_REQUIRE(d_x && d_ids && d_out_centroids && d_out_counts && d_ws, "kmeans_update: null argument");
   SRH_REQUIRE(n > 0 && n < (int64_t(1) << 31) && k > 0 && k < (int64_t(1) << 31) && d > 0, "kmeans_update: bad n / k / d");
   hipStream_t st = srh::as_stream(stream);
-  KmWs w = km_carve(static_cast<char*>(d_ws), n, k);
+  KmWs w;
+  km_layout(w, d_ws, n, k);
   SRH_HIP(hipMemsetAsync(w.chunk_cnt, 0, 4 * km_chunks(n) * k, st));
   km_rank<<<(unsigned)km_chunks(n), kKmChunk, 0, st>>>(d_ids, n, k, w);
   SRH_LAUNCH_CHECK();

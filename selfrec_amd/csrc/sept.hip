@@ -17,7 +17,7 @@
 //            bitmask of n bits per row.  The key of (i, j) is a function of rows i and j and of row i's two sums only,
 //            never of the tile, so identical aug rows tie exactly and the scan (ascending j, strict >) keeps the lower j.
 //   rowgrad  per view and row tile: Oout_i = sum_{j not in pos} e_ij a_j, Opos_i = sum_{j in pos} e_ij a_j and
-//            sum_{j in pos} e_ij in one sweep (two-MFMA form of contrastive.hip); with g = scale / tau,
+//            sum_{j in pos} e_ij in one sweep (the two products of rowtile.h); with g = scale / tau,
 //            dL/dv_i = g ((Oout_i + Opos_i) / sum_j e - Opos_i / sum_pos e), taken as
 //            g (Oout_i / sum_j e - Opos_i (sum_j e - sum_pos e) / (sum_j e sum_pos e)) with the factor in double;
 //            then the normalisation backward; the row's loss term and its two key-side weights
@@ -29,27 +29,18 @@
 #include <algorithm>
 #include <cmath>
 
-#include "common.h"
+#include "rowtile.h"
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+using namespace srh;
 
-constexpr int kWaves = 4;
-constexpr int kRows = 16 * kWaves;     // R rows per workgroup (16 per wave, in registers)
-constexpr int kCTile = 64;             // C rows staged in LDS per iteration
+constexpr int kRows = kRtRows;         // R rows per workgroup (16 per wave, in registers)
+constexpr int kCTile = kRtRows;        // C rows staged in LDS per iteration
 constexpr int kMaxK = 32;
 constexpr int kPass1Target = 512;      // pass-1 workgroups aimed for (3 views x row tiles x key chunks)
 constexpr float kSsEps = 1e-12f;       // tf.nn.l2_normalize's epsilon, on the squared norm
 constexpr float kInvClamp = 1e6f;      // rsqrt(1e-12)
-
-#define SRH_SUPPORTED(cond, ...)         \
-  do {                                   \
-    if (!(cond)) {                       \
-      ::srh::set_error(__VA_ARGS__);     \
-      return SRH_ERR_UNSUPPORTED;        \
-    }                                    \
-  } while (0)
 
 __device__ __forceinline__ float inv_norm(float ss) { return ss >= kSsEps ? 1.f / sqrtf(ss) : kInvClamp; }
 
@@ -143,33 +134,26 @@ inline int64_t tn_chunk_len(int64_t n) {
 }
 inline int64_t tn_words(int64_t n) { return (n + 31) / 32; }
 
-using srh::align256;
-
-inline int64_t tn_ws_bytes(int64_t n, int D) {
-  const int64_t c = tn_chunks(n);
-  return 4 * align256(4 * n * D) + 4 * align256(4 * n) + 2 * align256(8 * c * 3 * n) + align256(4 * 3 * n) +
-         align256(8 * 3 * n) + 2 * align256(4 * 3 * n) + align256(8 * 3 * n) + align256(4 * 3 * n * tn_words(n));
-}
-
-void tn_carve(TnArgs& p, char* ws, int D) {
-  char* cur = ws;
-  auto take = [&](int64_t bytes) { char* r = cur; cur += align256(bytes); return r; };
+// the workspace of p.n rows: null ws measures, a workspace carves; returns the bytes
+int64_t tn_layout(TnArgs& p, void* ws, int D) {
+  Carver w(ws);
   const int64_t n = p.n;
   p.chunks = tn_chunks(n);
   p.chunk_len = tn_chunk_len(n);
   p.words = tn_words(n);
-  for (int v = 0; v < 3; ++v) p.vn[v] = (float*)take(4 * n * D);
-  p.an = (float*)take(4 * n * D);
-  for (int v = 0; v < 3; ++v) p.vinv[v] = (float*)take(4 * n);
-  p.ainv = (float*)take(4 * n);
-  p.part1 = (double*)take(8 * p.chunks * 3 * n);
-  p.partT = (double*)take(8 * p.chunks * 3 * n);
-  p.inv1 = (float*)take(4 * 3 * n);
-  p.rsT = (double*)take(8 * 3 * n);
-  p.cw = (float*)take(4 * 3 * n);
-  p.cp = (float*)take(4 * 3 * n);
-  p.row_loss = (double*)take(8 * 3 * n);
-  p.mask = (uint32_t*)take(4 * 3 * n * p.words);
+  for (int v = 0; v < 3; ++v) w.take(p.vn[v], n * D);
+  w.take(p.an, n * D);
+  for (int v = 0; v < 3; ++v) w.take(p.vinv[v], n);
+  w.take(p.ainv, n);
+  w.take(p.part1, p.chunks * 3 * n);
+  w.take(p.partT, p.chunks * 3 * n);
+  w.take(p.inv1, 3 * n);
+  w.take(p.rsT, 3 * n);
+  w.take(p.cw, 3 * n);
+  w.take(p.cp, 3 * n);
+  w.take(p.row_loss, 3 * n);
+  w.take(p.mask, 3 * n * p.words);
+  return w.used;
 }
 
 // prep: LPR = D/4 lanes per row, one float4 each; blockIdx.y = matrix (views 0..2, then aug)
@@ -192,45 +176,16 @@ __global__ __launch_bounds__(256) void tn_prep(TnArgs a) {
   }
 }
 
-// C rows [c0, c0 + 64) of src (rows >= cend: zeros) into the LDS tile (contrastive.hip's staging)
-template <int D>
-__device__ __forceinline__ void stage_tile(float* cs, const float* __restrict__ src, int64_t c0, int64_t cend) {
-  constexpr int LDS_STRIDE = D + 4;
-  for (int e = threadIdx.x; e < kCTile * (D / 4); e += 256) {
-    const int i = e / (D / 4), q = e % (D / 4);
-    const int64_t c = c0 + i;
-    const float4 x = c < cend ? reinterpret_cast<const float4*>(src + c * D)[q] : srh::f4_zero();
-    *reinterpret_cast<float4*>(&cs[i * LDS_STRIDE + 4 * q]) = x;
-  }
-}
-
-// s[reg] = C[sub*16 + 4g + reg] . R[r]: A = the C tile from LDS, B = the R row from registers; k-steps in ascending order,
-// so the value depends on the two rows only
-template <int D>
-__device__ __forceinline__ f32x4 score16(const float* cs, int sub, int j16, int g, const float (&rf)[D / 4]) {
-  constexpr int LDS_STRIDE = D + 4;
-  f32x4 s = {0.f, 0.f, 0.f, 0.f};
-  const float* arow = &cs[(sub * 16 + j16) * LDS_STRIDE + g];
-#pragma unroll
-  for (int k = 0; k < D / 4; ++k) s = __builtin_amdgcn_mfma_f32_16x16x4f32(arow[4 * k], rf[k], s, 0, 0, 0);
-  return s;
-}
-
-template <int D>
-__device__ __forceinline__ void load_rf(float (&rf)[D / 4], const float* __restrict__ Rn, int64_t r, bool rok, int g) {
-#pragma unroll
-  for (int s = 0; s < D / 4; ++s) rf[s] = rok ? Rn[r * D + 4 * s + g] : 0.f;
-}
-
 template <int D>
 __global__ __launch_bounds__(256) void tn_pass1(TnArgs a) {
-  __shared__ float cs[kCTile * (D + 4)];
+  __shared__ float cs[kCTile * kRtStride<D>];
   const int v = blockIdx.y;
   const int64_t rtile = (int64_t)blockIdx.x / a.chunks, chunk = (int64_t)blockIdx.x % a.chunks;
   const int64_t cbeg = chunk * a.chunk_len;
   const int64_t cend = cbeg + a.chunk_len < a.n ? cbeg + a.chunk_len : a.n;
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, g = lane >> 4, j16 = lane & 15;
-  const int64_t r = rtile * kRows + wave * 16 + j16;
+  const RtLane L = rt_lane();
+  const int g = L.g, j16 = L.j16;
+  const int64_t r = rtile * kRows + L.wave * 16 + j16;
   const bool rok = r < a.n;
   const float inv_tau = a.inv_tau;
   float rf[D / 4];
@@ -252,10 +207,8 @@ __global__ __launch_bounds__(256) void tn_pass1(TnArgs a) {
       }
     }
   }
-  s1 += __shfl_xor(s1, 16);
-  s1 += __shfl_xor(s1, 32);
-  sT += __shfl_xor(sT, 16);
-  sT += __shfl_xor(sT, 32);
+  s1 = sum4(s1);
+  sT = sum4(sT);
   if (rok && g == 0) {
     a.part1[(chunk * 3 + v) * a.n + r] = s1;
     a.partT[(chunk * 3 + v) * a.n + r] = sT;
@@ -278,7 +231,7 @@ __global__ __launch_bounds__(256) void tn_rowsum(TnArgs a) {
 template <int D>
 __global__ __launch_bounds__(256) void tn_select(TnArgs a) {
   constexpr int DS = 17, LS = kMaxK + 1;
-  __shared__ float cs[kCTile * (D + 4)];
+  __shared__ float cs[kCTile * kRtStride<D>];
   __shared__ float dump[kRows * DS];
   __shared__ float lk[kRows * LS];
   __shared__ int32_t li[kRows * LS];
@@ -286,8 +239,9 @@ __global__ __launch_bounds__(256) void tn_select(TnArgs a) {
   const int va = t == 0 ? 1 : 0, vb = t == 2 ? 1 : 2;
   const int64_t n = a.n;
   const int64_t rtile = blockIdx.x;
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, g = lane >> 4, j16 = lane & 15;
-  const int64_t r = rtile * kRows + wave * 16 + j16;
+  const RtLane L = rt_lane();
+  const int g = L.g, j16 = L.j16;
+  const int64_t r = rtile * kRows + L.wave * 16 + j16;
   const bool rok = r < n;
   float rfa[D / 4], rfb[D / 4];
   load_rf<D>(rfa, a.vn[va], r, rok, g);
@@ -307,7 +261,7 @@ __global__ __launch_bounds__(256) void tn_select(TnArgs a) {
       const f32x4 sb = score16<D>(cs, sub, j16, g, rfb);
 #pragma unroll
       for (int reg = 0; reg < 4; ++reg)
-        dump[(wave * 16 + j16) * DS + 4 * g + reg] = fmaf(expf(sa[reg] - 1.f), ia, expf(sb[reg] - 1.f) * ib);
+        dump[(L.wave * 16 + j16) * DS + 4 * g + reg] = fmaf(expf(sa[reg] - 1.f), ia, expf(sb[reg] - 1.f) * ib);
       __syncthreads();
       if (threadIdx.x < kRows) {
         const int64_t j0 = c0 + sub * 16;
@@ -349,51 +303,23 @@ __global__ __launch_bounds__(256) void tn_select(TnArgs a) {
   }
 }
 
-// the normalisation backward of a row held as o[b][reg] = G[r][16b + 4g + reg] (four lanes g = 0..3 share the row)
-template <int D>
-__device__ __forceinline__ void norm_bwd_store(f32x4 (&o)[D / 16], const float* __restrict__ yn, float inv, int64_t r,
-                                               bool rok, int g, float* __restrict__ dst) {
-  float4 y[D / 16];
-  float dot = 0.f;
-#pragma unroll
-  for (int b = 0; b < D / 16; ++b) {
-    y[b] = rok ? reinterpret_cast<const float4*>(yn + r * D + 16 * b + 4 * g)[0] : srh::f4_zero();
-    dot = fmaf(y[b].x, o[b][0], fmaf(y[b].y, o[b][1], fmaf(y[b].z, o[b][2], fmaf(y[b].w, o[b][3], dot))));
-  }
-  dot += __shfl_xor(dot, 16);
-  dot += __shfl_xor(dot, 32);
-  if (!rok) return;
-  const bool clamped = inv == kInvClamp;
-#pragma unroll
-  for (int b = 0; b < D / 16; ++b) {
-    float4 out;
-    if (clamped) {
-      out = make_float4(o[b][0] * inv, o[b][1] * inv, o[b][2] * inv, o[b][3] * inv);
-    } else {
-      out = make_float4((o[b][0] - y[b].x * dot) * inv, (o[b][1] - y[b].y * dot) * inv, (o[b][2] - y[b].z * dot) * inv,
-                        (o[b][3] - y[b].w * dot) * inv);
-    }
-    reinterpret_cast<float4*>(dst + r * D + 16 * b + 4 * g)[0] = out;
-  }
-}
-
 template <int D>
 __global__ __launch_bounds__(256) void tn_rowgrad(TnArgs a) {
-  constexpr int LDS_STRIDE = D + 4;
-  __shared__ float cs[kCTile * LDS_STRIDE];
+  __shared__ float cs[kCTile * kRtStride<D>];
   const int v = blockIdx.y;
   const int64_t n = a.n;
   const int64_t rtile = blockIdx.x;
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, g = lane >> 4, j16 = lane & 15;
-  const int64_t r = rtile * kRows + wave * 16 + j16;
+  const RtLane L = rt_lane();
+  const int g = L.g, j16 = L.j16;
+  const int64_t r = rtile * kRows + L.wave * 16 + j16;
   const bool rok = r < n;
   const float inv_tau = a.inv_tau;
   float rf[D / 4];
   load_rf<D>(rf, a.vn[v], r, rok, g);
   const uint32_t* mrow = a.mask + ((int64_t)v * n + (rok ? r : 0)) * a.words;
   f32x4 o1[D / 16], o2[D / 16];
-#pragma unroll
-  for (int b = 0; b < D / 16; ++b) o1[b] = o2[b] = f32x4{0.f, 0.f, 0.f, 0.f};
+  zero_acc(o1);
+  zero_acc(o2);
   double sp = 0.0;
   for (int64_t c0 = 0; c0 < n; c0 += kCTile) {
     __syncthreads();
@@ -416,20 +342,20 @@ __global__ __launch_bounds__(256) void tn_rowgrad(TnArgs a) {
         s[reg] = in ? 0.f : e;   // o1: the keys off the list; o2: the positives
         sm[reg] = in ? e : 0.f;
       }
+      // (accum16 for both sums at once, spelled out so that the two accumulator chains alternate; two accum16 calls give
+      // the same bits and measured level at d = 64 and 0.2 % over the limit at d = 128: profiles/NOTES_rowtile.md)
 #pragma unroll
       for (int b = 0; b < D / 16; ++b) {
 #pragma unroll
         for (int reg = 0; reg < 4; ++reg) {
-          const float x = cs[(sub * 16 + 4 * g + reg) * LDS_STRIDE + 16 * b + j16];
+          const float x = cs[(sub * 16 + 4 * g + reg) * kRtStride<D> + 16 * b + j16];
           o1[b] = __builtin_amdgcn_mfma_f32_16x16x4f32(x, s[reg], o1[b], 0, 0, 0);
           o2[b] = __builtin_amdgcn_mfma_f32_16x16x4f32(x, sm[reg], o2[b], 0, 0, 0);
         }
       }
     }
   }
-  // o[b][reg] = O[r][16b + 4g + reg]
-  sp += __shfl_xor(sp, 16);
-  sp += __shfl_xor(sp, 32);
+  sp = sum4(sp);
   const int64_t e = (int64_t)v * n + (rok ? r : 0);
   const double rsT = rok ? a.rsT[e] : 1.0;
   const float cw = (float)(1.0 / rsT);
@@ -445,28 +371,28 @@ __global__ __launch_bounds__(256) void tn_rowgrad(TnArgs a) {
     a.cp[e] = (float)(1.0 / sp);
     a.row_loss[e] = log(rsT) - log(sp);
   }
-  norm_bwd_store<D>(o1, a.vn[v], rok ? a.vinv[v][r] : 1.f, r, rok, g, a.gv[v]);
+  const float inv = rok ? a.vinv[v][r] : 1.f;
+  norm_bwd_store<D>(o1, a.vn[v], inv, inv == kInvClamp, r, rok, g, a.gv[v]);
 }
 
 template <int D>
 __global__ __launch_bounds__(256) void tn_keygrad(TnArgs a) {
-  constexpr int LDS_STRIDE = D + 4;
-  __shared__ float cs[kCTile * LDS_STRIDE];
+  __shared__ float cs[kCTile * kRtStride<D>];
   __shared__ float cwl[kCTile];
   __shared__ float cpl[kCTile];
   __shared__ uint32_t ml[kCTile * 2];
   const int64_t n = a.n;
   const int64_t rtile = blockIdx.x;
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, g = lane >> 4, j16 = lane & 15;
-  const int lr = wave * 16 + j16;            // this lane's key within the tile
+  const RtLane L = rt_lane();
+  const int g = L.g, j16 = L.j16;
+  const int lr = L.wave * 16 + j16;          // this lane's key within the tile
   const int64_t r = rtile * kRows + lr;
   const bool rok = r < n;
   const float inv_tau = a.inv_tau;
   float rf[D / 4];
   load_rf<D>(rf, a.an, r, rok, g);
   f32x4 o[D / 16];
-#pragma unroll
-  for (int b = 0; b < D / 16; ++b) o[b] = f32x4{0.f, 0.f, 0.f, 0.f};
+  zero_acc(o);
   const int64_t wbase = rtile * (kRows / 32);  // the two mask words that hold this tile's keys
   for (int v = 0; v < 3; ++v) {
     for (int64_t c0 = 0; c0 < n; c0 += kCTile) {
@@ -495,12 +421,14 @@ __global__ __launch_bounds__(256) void tn_keygrad(TnArgs a) {
           const float wp = e * cpl[ci];
           s[reg] = e * cwl[ci] - (in ? wp : 0.f);
         }
+        // (accum16's product, spelled out: through the helper this kernel's code is reordered and the step measured
+        // 2 % slower, profiles/NOTES_rowtile.md)
 #pragma unroll
         for (int b = 0; b < D / 16; ++b) {
 #pragma unroll
           for (int reg = 0; reg < 4; ++reg)
-            o[b] = __builtin_amdgcn_mfma_f32_16x16x4f32(cs[(sub * 16 + 4 * g + reg) * LDS_STRIDE + 16 * b + j16], s[reg],
-                                                        o[b], 0, 0, 0);
+            o[b] = __builtin_amdgcn_mfma_f32_16x16x4f32(cs[(sub * 16 + 4 * g + reg) * kRtStride<D> + 16 * b + j16], s[reg], o[b],
+                                                        0, 0, 0);
         }
       }
     }
@@ -508,22 +436,15 @@ __global__ __launch_bounds__(256) void tn_keygrad(TnArgs a) {
   const float gs = a.gscale;
 #pragma unroll
   for (int b = 0; b < D / 16; ++b) o[b] *= gs;
-  norm_bwd_store<D>(o, a.an, rok ? a.ainv[r] : 1.f, r, rok, g, a.ga);
+  const float inv = rok ? a.ainv[r] : 1.f;
+  norm_bwd_store<D>(o, a.an, inv, inv == kInvClamp, r, rok, g, a.ga);
 }
 
 // the loss of view blockIdx.x: its row terms in a fixed order, times the scale
 __global__ __launch_bounds__(256) void tn_loss(TnArgs a) {
-  __shared__ double part[256];
   const int v = blockIdx.x;
-  double s = 0.0;
-  for (int64_t b = threadIdx.x; b < a.n; b += 256) s += a.row_loss[(int64_t)v * a.n + b];
-  part[threadIdx.x] = s;
-  __syncthreads();
-  for (int w = 128; w > 0; w >>= 1) {
-    if ((int)threadIdx.x < w) part[threadIdx.x] += part[threadIdx.x + w];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) a.loss[v] = (double)a.scale * part[0];
+  const double s = block_sum_d(a.row_loss + (int64_t)v * a.n, a.n);
+  if (threadIdx.x == 0) a.loss[v] = (double)a.scale * s;
 }
 
 template <int D>
@@ -574,7 +495,9 @@ srh_status_t srh_rows_l2norm_bwd_f32(const float* d_g, const float* d_out, const
 
 int64_t srh_tri_nd_ws_bytes(int64_t n, int32_t d, int32_t k) {
   if (n <= 0 || n >= (int64_t(1) << 24) || (d != 64 && d != 128) || k < 1 || k > kMaxK || n < k) return 0;
-  return tn_ws_bytes(n, d);
+  TnArgs a{};
+  a.n = n;
+  return tn_layout(a, nullptr, d);
 }
 
 srh_status_t srh_tri_nd_fwd_bwd(const srh_tri_nd_args_t* args, void* d_ws, void* stream) {
@@ -599,7 +522,7 @@ srh_status_t srh_tri_nd_fwd_bwd(const srh_tri_nd_args_t* args, void* d_ws, void*
   a.scale = s.loss_scale;
   a.gscale = s.loss_scale * a.inv_tau;
   a.loss = s.d_loss; a.ga = s.d_gaug; a.pos = s.d_pos;
-  tn_carve(a, static_cast<char*>(d_ws), s.d);
+  tn_layout(a, d_ws, s.d);
   hipStream_t st = srh::as_stream(stream);
   return s.d == 64 ? launch_tn<64>(a, st) : launch_tn<128>(a, st);
 }

@@ -46,14 +46,6 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 constexpr int kMaxL = 64;        // query / key rows a workgroup holds
 constexpr int kLdX = kMaxL + 8;  // LDS row stride (floats) of the P~ / dS buffer of the backward's second pass
 
-#define SRH_SUPPORTED(cond, ...)         \
-  do {                                   \
-    if (!(cond)) {                       \
-      ::srh::set_error(__VA_ARGS__);     \
-      return SRH_ERR_UNSUPPORTED;        \
-    }                                    \
-  } while (0)
-
 enum { DROP_NONE = 0, DROP_GIVEN = 1, DROP_DRAWN = 2 };
 
 struct AttnArgs {

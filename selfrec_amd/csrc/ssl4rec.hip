@@ -11,29 +11,25 @@
 //                       (optional): injected, or drawn from the counter RNG of the SpMM epilogue (common.h).  H and the
 //                       effective input are written for the backward pass.
 //   srh_tower_bwd_f32   dZ2 = dY (1 - Y^2); dZ1 = (dZ2 W2) [H > 0]; dX = (dZ1 W1) m  (m: the dropout multiplier);
-//                       dW2 = dZ2^T H, dW1 = dZ1^T X, db2 / db1 the column sums.  The products run on one strided MFMA
-//                       GEMM kernel; the reductions over rows are cut into fixed chunks of kRowChunk rows whose partials
-//                       are summed in chunk order: no float atomics, the same bits on every call.
+//                       dW2 = dZ2^T H, dW1 = dZ1^T X, db2 / db1 the column sums.  The products run on the strided MFMA
+//                       GEMM of chunked.hip; the reductions over rows are cut into fixed chunks of kRowChunk rows whose
+//                       partials are summed in chunk order (chunked.hip): no float atomics, the same bits on every call.
 //   srh_rows_segment_sum_f32  the deterministic scatter of dX into the embedding-table gradient: rows grouped by the
 //                       host's stable sort of the ids, each table row sums its rows in that order.
 //
 // batch_softmax_loss (srh_batch_softmax_fwd_bwd) is the shared two-pass kernel of contrastive.hip.
 #include <algorithm>
 
-#include "common.h"
+#include "rowtile.h"
 
 namespace {
 
 using namespace srh;
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int kIn = 64, kHid = 1024, kOut = 128;
 constexpr int kHc = 64;                 // hidden units per chunk of the forward walk
 constexpr int kLds = kHc + 4;           // LDS row stride (floats) of the staged chunk
 constexpr int kRowChunk = 256;          // rows per partial of the weight-gradient reductions
-
-__host__ __device__ inline int64_t row_chunks(int64_t n) { return (n + kRowChunk - 1) / kRowChunk; }
 
 struct FwdArgs {
   const float* table;
@@ -139,102 +135,11 @@ __global__ __launch_bounds__(256) void tw_fwd(FwdArgs a) {
 }
 
 // ---- tower backward ----------------------------------------------------------------------------------------------------
-enum { EPI_STORE = 0, EPI_RELU = 1, EPI_MASK = 2 };
-
-// C (M x N) = A (M x K) B (K x N) with element strides; blockIdx.z takes rows [z kchunk, (z + 1) kchunk) of K and writes
-// its own slab C + z c_zstride.  64 x 64 tile per workgroup, 16 rows of it per wave, K staged 16 at a time.
-struct GemmArgs {
-  const float* A;
-  int64_t sam, sak;
-  const float* B;
-  int64_t sbk, sbn;
-  float* C;
-  int64_t ldc, c_zstride;
-  int64_t M, N, K, kchunk;
-  const float* aux;      // EPI_RELU: C *= (aux[m ldc + n] > 0)
-  const uint8_t* mask;   // EPI_MASK: rows m >= mask_row0: C *= mask[(m - mask_row0) N + n] ? mask_scale : 0
-  int64_t mask_row0;
-  float mask_scale;
-};
-
-template <int EPI>
-__global__ __launch_bounds__(256) void tw_gemm(GemmArgs a) {
-  __shared__ float as[64 * 17];   // as[m][k]
-  __shared__ float bs[16 * 68];   // bs[k][n]
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, g = lane >> 4, j16 = lane & 15;
-  const int64_t m0 = (int64_t)blockIdx.y * 64, n0 = (int64_t)blockIdx.x * 64;
-  const int64_t kb = (int64_t)blockIdx.z * a.kchunk;
-  const int64_t ke = std::min(kb + a.kchunk, a.K);
-  const bool a_krow = a.sak == 1, b_nrow = a.sbn == 1;
-  f32x4 acc[4];
-#pragma unroll
-  for (int t = 0; t < 4; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-  for (int64_t k0 = kb; k0 < ke; k0 += 16) {
-    __syncthreads();
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int e = threadIdx.x + 256 * u;
-      int m, k;
-      if (a_krow) { m = e / 16; k = e % 16; } else { m = e % 64; k = e / 64; }
-      const int64_t gm = m0 + m, gk = k0 + k;
-      as[m * 17 + k] = (gm < a.M && gk < ke) ? a.A[gm * a.sam + gk * a.sak] : 0.f;
-      int n;
-      if (b_nrow) { k = e / 64; n = e % 64; } else { n = e / 16; k = e % 16; }
-      const int64_t gk2 = k0 + k, gn = n0 + n;
-      bs[k * 68 + n] = (gk2 < ke && gn < a.N) ? a.B[gk2 * a.sbk + gn * a.sbn] : 0.f;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const float av = as[(16 * wave + j16) * 17 + 4 * q + g];
-#pragma unroll
-      for (int t = 0; t < 4; ++t)
-        acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bs[(4 * q + g) * 68 + 16 * t + j16], acc[t], 0, 0, 0);
-    }
-  }
-  float* C = a.C + (int64_t)blockIdx.z * a.c_zstride;
-#pragma unroll
-  for (int t = 0; t < 4; ++t) {
-    const int64_t n = n0 + 16 * t + j16;
-#pragma unroll
-    for (int reg = 0; reg < 4; ++reg) {
-      const int64_t m = m0 + 16 * wave + 4 * g + reg;
-      if (m >= a.M || n >= a.N) continue;
-      float v = acc[t][reg];
-      if (EPI == EPI_RELU) v = a.aux[m * a.ldc + n] > 0.f ? v : 0.f;
-      if (EPI == EPI_MASK && m >= a.mask_row0) v = v * (a.mask[(m - a.mask_row0) * a.N + n] ? a.mask_scale : 0.f);
-      C[m * a.ldc + n] = v;
-    }
-  }
-}
-
 // dZ2 = dY (1 - Y^2) (torch's tanh_backward)
 __global__ __launch_bounds__(256) void tw_tanh_bwd(const float* __restrict__ gy, const float* __restrict__ y, int64_t len,
                                                    float* __restrict__ dz) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i < len) dz[i] = gy[i] * (1.f - y[i] * y[i]);
-}
-
-// part[c][e] = sum over rows r of chunk c, ascending, of x[r][e]  (x: n x len)
-__global__ __launch_bounds__(256) void tw_colsum_part(const float* __restrict__ x, int64_t n, int64_t len,
-                                                      float* __restrict__ part) {
-  const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  const int64_t c = blockIdx.y;
-  if (e >= len) return;
-  const int64_t r1 = std::min((c + 1) * kRowChunk, n);
-  float s = 0.f;
-  for (int64_t r = c * kRowChunk; r < r1; ++r) s += x[r * len + e];
-  part[c * len + e] = s;
-}
-
-// out[e] = sum over c, ascending, of part[c][e]
-__global__ __launch_bounds__(256) void tw_reduce(const float* __restrict__ part, int64_t chunks, int64_t len,
-                                                 float* __restrict__ out) {
-  const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (e >= len) return;
-  float s = 0.f;
-  for (int64_t c = 0; c < chunks; ++c) s += part[c * len + e];
-  out[e] = s;
 }
 
 // one wave per segment: table row seg_row[s] += sum of rows order[seg_start[s] .. seg_start[s + 1]) of x, in that order
@@ -257,14 +162,6 @@ __global__ __launch_bounds__(256) void seg_sum(const float* __restrict__ x, int3
   }
 }
 
-template <int EPI>
-srh_status_t gemm(const GemmArgs& a, int64_t zchunks, hipStream_t st) {
-  const dim3 grid((unsigned)((a.N + 63) / 64), (unsigned)((a.M + 63) / 64), (unsigned)zchunks);
-  tw_gemm<EPI><<<grid, 256, 0, st>>>(a);
-  SRH_LAUNCH_CHECK();
-  return SRH_OK;
-}
-
 struct BwdWs {
   float* dz2;     // n x 128
   float* dz1;     // n x 1024
@@ -272,22 +169,15 @@ struct BwdWs {
   float* part_b;  // chunks x (1024 + 128)
 };
 
-inline int64_t bwd_ws_bytes(int64_t n) {
-  const int64_t c = row_chunks(n);
-  return align256(4 * n * kOut) + align256(4 * n * kHid) + align256(4 * c * (kHid * kIn + kOut * kHid)) +
-         align256(4 * c * (kHid + kOut));
-}
-
-BwdWs bwd_carve(char* ws, int64_t n) {
-  BwdWs w;
-  char* cur = ws;
-  auto take = [&](int64_t bytes) { char* r = cur; cur += align256(bytes); return r; };
-  const int64_t c = row_chunks(n);
-  w.dz2 = (float*)take(4 * n * kOut);
-  w.dz1 = (float*)take(4 * n * kHid);
-  w.part_w = (float*)take(4 * c * (kHid * kIn + kOut * kHid));
-  w.part_b = (float*)take(4 * c * (kHid + kOut));
-  return w;
+// null ws measures, a workspace carves; returns the bytes
+int64_t bwd_layout(BwdWs& w, void* ws, int64_t n) {
+  Carver cv(ws);
+  const int64_t c = ceil_div(n, kRowChunk);
+  cv.take(w.dz2, n * kOut);
+  cv.take(w.dz1, n * kHid);
+  cv.take(w.part_w, c * (kHid * kIn + kOut * kHid));
+  cv.take(w.part_b, c * (kHid + kOut));
+  return cv.used;
 }
 
 srh_status_t check_weights(const srh_tower_weights_t* w) {
@@ -325,7 +215,8 @@ srh_status_t srh_tower_fwd_f32(const float* d_table, const int32_t* d_idx, int64
 
 int64_t srh_tower_bwd_ws_bytes(int64_t n) {
   if (n <= 0) return 0;
-  return bwd_ws_bytes(n);
+  BwdWs w;
+  return bwd_layout(w, nullptr, n);
 }
 
 srh_status_t srh_tower_bwd_f32(const float* d_x, const float* d_hidden, const float* d_y, const float* d_gy, int64_t n,
@@ -340,8 +231,9 @@ srh_status_t srh_tower_bwd_f32(const float* d_x, const float* d_hidden, const fl
   const srh_status_t wst = check_weights(w);
   if (wst != SRH_OK) return wst;
   hipStream_t st = as_stream(stream);
-  BwdWs ws = bwd_carve(static_cast<char*>(d_ws), n);
-  const int64_t chunks = row_chunks(n);
+  BwdWs ws;
+  bwd_layout(ws, d_ws, n);
+  const int64_t chunks = ceil_div(n, kRowChunk);
   srh_status_t s;
   // dZ2
   tw_tanh_bwd<<<(unsigned)((n * kOut + 255) / 256), 256, 0, st>>>(d_gy, d_y, n * kOut, ws.dz2);
@@ -350,42 +242,35 @@ srh_status_t srh_tower_bwd_f32(const float* d_x, const float* d_hidden, const fl
   GemmArgs g{};
   g.A = ws.dz2; g.sam = kOut; g.sak = 1; g.B = w->d_w2; g.sbk = kHid; g.sbn = 1; g.C = ws.dz1; g.ldc = kHid; g.M = n; g.N = kHid; g.K = kOut; g.kchunk = kOut;
   g.aux = d_hidden;
-  if ((s = gemm<EPI_RELU>(g, 1, st)) != SRH_OK) return s;
+  if ((s = gemm64(g, EPI_RELU, 1, st)) != SRH_OK) return s;
   // dX = (dZ1 W1) m                (n x 1024) (1024 x 64)
   g = GemmArgs{};
   g.A = ws.dz1; g.sam = kHid; g.sak = 1; g.B = w->d_w1; g.sbk = kIn; g.sbn = 1; g.C = d_gx; g.ldc = kIn;
   g.M = n; g.N = kIn; g.K = kHid; g.kchunk = kHid;
   g.mask = d_mask; g.mask_row0 = d_mask ? mask_row0 : n; g.mask_scale = 1.f / (1.f - drop_p);
-  if ((s = d_mask ? gemm<EPI_MASK>(g, 1, st) : gemm<EPI_STORE>(g, 1, st)) != SRH_OK) return s;
+  if ((s = gemm64(g, d_mask ? EPI_MASK : EPI_STORE, 1, st)) != SRH_OK) return s;
   // dW1 partials = dZ1^T X per chunk of rows     (1024 x n) (n x 64)
   float* part_w1 = ws.part_w;
   float* part_w2 = ws.part_w + chunks * kHid * kIn;
   g = GemmArgs{};
   g.A = ws.dz1; g.sam = 1; g.sak = kHid; g.B = d_x; g.sbk = kIn; g.sbn = 1; g.C = part_w1; g.ldc = kIn;
   g.c_zstride = kHid * kIn; g.M = kHid; g.N = kIn; g.K = n; g.kchunk = kRowChunk;
-  if ((s = gemm<EPI_STORE>(g, chunks, st)) != SRH_OK) return s;
+  if ((s = gemm64(g, EPI_STORE, chunks, st)) != SRH_OK) return s;
   // dW2 partials = dZ2^T H per chunk of rows     (128 x n) (n x 1024)
   g = GemmArgs{};
   g.A = ws.dz2; g.sam = 1; g.sak = kOut; g.B = d_hidden; g.sbk = kHid; g.sbn = 1; g.C = part_w2; g.ldc = kHid;
   g.c_zstride = kOut * kHid; g.M = kOut; g.N = kHid; g.K = n; g.kchunk = kRowChunk;
-  if ((s = gemm<EPI_STORE>(g, chunks, st)) != SRH_OK) return s;
+  if ((s = gemm64(g, EPI_STORE, chunks, st)) != SRH_OK) return s;
   // bias partials
   float* part_b1 = ws.part_b;
   float* part_b2 = ws.part_b + chunks * kHid;
-  tw_colsum_part<<<dim3(kHid / 256, (unsigned)chunks), 256, 0, st>>>(ws.dz1, n, kHid, part_b1);
-  SRH_LAUNCH_CHECK();
-  tw_colsum_part<<<dim3(1, (unsigned)chunks), 256, 0, st>>>(ws.dz2, n, kOut, part_b2);
-  SRH_LAUNCH_CHECK();
+  if ((s = colsum_chunks(ws.dz1, n, kHid, 1, kRowChunk, part_b1, st)) != SRH_OK) return s;
+  if ((s = colsum_chunks(ws.dz2, n, kOut, 1, kRowChunk, part_b2, st)) != SRH_OK) return s;
   // the partials in chunk order
-  tw_reduce<<<(unsigned)((kHid * kIn + 255) / 256), 256, 0, st>>>(part_w1, chunks, kHid * kIn, d_gw1);
-  SRH_LAUNCH_CHECK();
-  tw_reduce<<<(unsigned)((kOut * kHid + 255) / 256), 256, 0, st>>>(part_w2, chunks, kOut * kHid, d_gw2);
-  SRH_LAUNCH_CHECK();
-  tw_reduce<<<(unsigned)(kHid / 256), 256, 0, st>>>(part_b1, chunks, kHid, d_gb1);
-  SRH_LAUNCH_CHECK();
-  tw_reduce<<<1, 256, 0, st>>>(part_b2, chunks, kOut, d_gb2);
-  SRH_LAUNCH_CHECK();
-  return SRH_OK;
+  if ((s = reduce_chunks(part_w1, chunks, kHid * kIn, 1.f, d_gw1, st)) != SRH_OK) return s;
+  if ((s = reduce_chunks(part_w2, chunks, kOut * kHid, 1.f, d_gw2, st)) != SRH_OK) return s;
+  if ((s = reduce_chunks(part_b1, chunks, kHid, 1.f, d_gb1, st)) != SRH_OK) return s;
+  return reduce_chunks(part_b2, chunks, kOut, 1.f, d_gb2, st);
 }
 
 srh_status_t srh_rows_segment_sum_f32(const float* d_x, int64_t n_rows, int32_t d, const int32_t* d_order,
