@@ -1,4 +1,4 @@
-"""MHCN on the GPU against the float64 restatement tests/mhcn_ref.py, through the C ABI wrappers of selfrec_amd/ops.py: the
+"""MHCN on the GPU against the float64 restatement tests/mhcn_ref.py, through the C ABI wrappers of selfrec_amd/ops/mhcn.py: the
 gate kernels on every shape, the channel mix and the MIM loss on ordinary inputs (their edge families are in
 tests/test_gpu_mhcn_edges.py), the autograd functions, and the model's step, routes and training on the tiny synthetic graph
 with generated trust pairs."""
