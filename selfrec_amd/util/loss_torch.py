@@ -7,7 +7,8 @@ What runs where:
     HIP kernels; a missing library or device raises (``ops.SelfrecHipError``), nothing is substituted.  Any
     ``embedding.size`` (base/recommender.py:16): rows are zero-padded to the next width the kernels serve -- zero
     columns change no inner product, norm or F.normalize result and receive exactly zero gradient -- BPR up to
-    256 columns, InfoNCE up to 256 (above 128: the split path only), the regulariser any size.
+    256 columns, InfoNCE up to 256 (above 128: the split path only), the regulariser any size.  bpr_loss's three operands
+    broadcast against each other as the reference's torch.mul does (_bpr_operands); no rows: the torch expression (nan).
   * CPU tensors, other dtypes, other ranks: the reference's own torch expression (the arithmetic of loss_torch.py:6-50
     restated below), so code that calls these functions off the device -- unit tests of a model file, a CPU dry run --
     behaves as it does with the reference.  This is not a fallback for the HIP path: device fp32 input never reaches it.
@@ -76,17 +77,30 @@ def _announce_wide(what, d, limit):
                       f"expression (util/loss_torch.py) with ATen on the device", RuntimeWarning, stacklevel=3)
 
 
+def _bpr_operands(user_emb, pos_item_emb, neg_item_emb):
+    """The three operands at one shape, as the reference's torch.mul(user_emb, item_emb) sees them: equal shapes pass
+    through, shapes that broadcast are expanded (views, OUTSIDE the autograd Function: autograd sums the gradient back
+    over the expanded axis), anything else raises what torch raises.  The kernels take B and the width from one operand
+    and cannot know the others' (pad_cols makes the expanded views contiguous)."""
+    if user_emb.shape == pos_item_emb.shape == neg_item_emb.shape:
+        return user_emb, pos_item_emb, neg_item_emb
+    return tuple(torch.broadcast_tensors(user_emb, pos_item_emb, neg_item_emb))
+
+
 def bpr_loss(user_emb, pos_item_emb, neg_item_emb):
-    wide = _on_hip_path(user_emb) and int(user_emb.shape[1]) > ops.ROW_WIDTHS[-1]
-    if wide:
-        _announce_wide("bpr_loss", int(user_emb.shape[1]), ops.ROW_WIDTHS[-1])
-    if wide or not _on_hip_path(user_emb, pos_item_emb, neg_item_emb):
-        # loss_torch.py:6-10
-        pos_score = torch.mul(user_emb, pos_item_emb).sum(dim=1)
-        neg_score = torch.mul(user_emb, neg_item_emb).sum(dim=1)
-        loss = -torch.log(10e-6 + torch.sigmoid(pos_score - neg_score))
-        return torch.mean(loss)
-    return _BprFn.apply(user_emb, pos_item_emb, neg_item_emb)
+    if _on_hip_path(user_emb, pos_item_emb, neg_item_emb):
+        u, p, n = _bpr_operands(user_emb, pos_item_emb, neg_item_emb)
+        rows, d = int(u.shape[0]), int(u.shape[1])
+        if rows > 0 and d <= ops.ROW_WIDTHS[-1]:
+            return _BprFn.apply(u, p, n)
+        if d > ops.ROW_WIDTHS[-1]:
+            _announce_wide("bpr_loss", d, ops.ROW_WIDTHS[-1])
+        # (no rows: the mean of nothing, nan, as the reference returns -- the expression below)
+    # loss_torch.py:6-10
+    pos_score = torch.mul(user_emb, pos_item_emb).sum(dim=1)
+    neg_score = torch.mul(user_emb, neg_item_emb).sum(dim=1)
+    loss = -torch.log(10e-6 + torch.sigmoid(pos_score - neg_score))
+    return torch.mean(loss)
 
 
 class _L2RegFn(torch.autograd.Function):

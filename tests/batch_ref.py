@@ -40,6 +40,15 @@ def logits(user, item, u, i, j):
     return (uu * _f64(item)[i]).sum(1) - (uu * _f64(item)[j]).sum(1)
 
 
+def bpr_terms(x):
+    """sigmoid(x), 1 - sigmoid(x) (its own expression: no cancellation at large x) and the logarithm's argument 10e-6 + sigmoid(x)
+    of loss_torch.py:9, float64 (tests/loss_ref.py shares them)"""
+    with np.errstate(over="ignore"):
+        sig = 1.0 / (1.0 + np.exp(-x))
+        one_minus = 1.0 / (1.0 + np.exp(x))
+    return sig, one_minus, 10e-6 + sig
+
+
 def bpr_l2(user, item, reg_user, reg_item, u, i, j, reg_coef, include_neg, loss_scale):
     """loss_torch.py's bpr_loss (-log(10e-6 + sigmoid(x)), mean over rows) and l2_reg_loss (sum of Frobenius norms / rows) of the
     gathered rows with the gradients of loss_scale * (bpr + reg) w.r.t. the four tables, in float64.  A zero norm gives a zero
@@ -51,10 +60,7 @@ def bpr_l2(user, item, reg_user, reg_item, u, i, j, reg_coef, include_neg, loss_
     rows = u.size
     uu, pp, nn = U[u], I[i], I[j]
     x = (uu * pp).sum(1) - (uu * nn).sum(1)
-    with np.errstate(over="ignore"):
-        sig = 1.0 / (1.0 + np.exp(-x))
-        one_minus = 1.0 / (1.0 + np.exp(x))
-    arg = 10e-6 + sig
+    sig, one_minus, arg = bpr_terms(x)
     out = {"x": x, "bpr": loss_scale * np.mean(-np.log(arg))}
     c = (-(sig * one_minus) / arg) * (loss_scale / rows)
     g_user, g_item = np.zeros_like(U), np.zeros_like(I)
