@@ -1130,6 +1130,44 @@ srh_status_t srh_mixup_bwd_f32(const srh_mixup_args_t* args, const int32_t* d_pi
                                const float* d_g_neg, void* d_ws, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * (a-22) DirectAU -- the alignment and uniformity losses of model/graph/DirectAU.py:37-48 on the batch's gathered rows,
+ * forward and backward in one call, with no n x n matrix (and no list of n (n - 1) / 2 distances) in memory.
+ * x and y: n x d float32, row-major, un-normalised.  With xh_i = x_i / max(|x_i|, 1e-12) (F.normalize):
+ *     A(x, y) = mean_i |xh_i - yh_i|^2
+ *     U(x)    = log( mean_{i<j} exp(-t |xh_i - xh_j|^2) )
+ *     loss    = w_align A(x, y) + w_ux U(x) + w_uy U(y)
+ *   taken in closed form: q_i = |xh_i|^2 (1 for an ordinary row, below 1 where the norm was clamped), s_ij = xh_i . xh_j,
+ *     w_ij = exp(-t max(0, q_i + q_j - 2 s_ij)) for j != i, w_ii = 0;  r_i = sum_j w_ij;  Z = sum_i r_i;
+ *     U = log(Z / (n (n - 1)));  dU/dxh_i = (4 t / Z) (sum_j w_ij xh_j - r_i xh_i);  dA/dxh_i = 2 (xh_i - yh_i) / n = -dA/dyh_i
+ *   and through the normalisation (G - xh (xh . G)) / |x|, or G 1e12 where the norm was clamped (there the radial part
+ *   r_i xh_i stays; on an ordinary row the projection removes it, so it is not formed).  The exponent is never positive:
+ *   no running maximum.  Duplicate rows (a batch repeats users) weigh 1 and pull nothing.
+ * srh_au_fwd_bwd READS d_x and d_y and WRITES, by plain stores, every element of d_gx and d_gy (n x d, dloss/dx and
+ *   dloss/dy), d_parts[0..2] = A, U(x), U(y) unweighted, and d_loss[0] (doubles on the device).  d_y == NULL: U(x) alone --
+ *   loss = w_ux U(x); w_align and w_uy are ignored and d_gy, d_parts[0] and d_parts[2] are not touched.  Neither the
+ *   outputs nor the workspace need any initialisation by the caller.
+ * Launches: prep (both sides: xh, 1 / max(|x|, 1e-12), q, the row's alignment term), the self-Gram pass (64-row tiles
+ *   x key chunks x sides on v_mfma_f32_16x16x4_f32: the tile's rows in registers, the SAME matrix streamed through LDS,
+ *   the weight taken on the accumulator and fed to the second product; own index and rows >= n weigh exactly 0), a
+ *   reduction (r_i over the chunks in chunk order, then Z, A and the parts in a fixed order), the finish (chunk partials
+ *   summed in chunk order, both gradients, the normalisation backward, the loss).  No float atomics; every sum has one
+ *   order: a call returns the same bits every time.
+ * Chunk plan (srh_au_chunk_plan; a function of n alone): tiles = ceil(n / 64), chunks = max(1, min(tiles,
+ *   ceil(512 / (2 tiles)))), chunk_len = ceil(ceil(n / chunks) / 64) 64 keys; chunk c holds keys [c chunk_len,
+ *   min(n, (c + 1) chunk_len)), which may be empty for trailing chunks (it then writes zeros).
+ * Envelope: d = 64 or 128 (zero-pad narrower rows: a padded column changes no result), else SRH_ERR_UNSUPPORTED with a
+ *   message; 2 <= n < 2^24 (n < 2 is SRH_ERR_INVALID_ARG: the reference gives nan there); t > 0 and finite, the weights
+ *   finite.  All arguments are checked before any launch.  d_ws >= srh_au_ws_bytes(n, d) (0 for a shape the kernels do
+ *   not serve): two normalised copies, 3 floats and 1 double per row and side, and per chunk and side n doubles and n x d
+ *   floats.
+ * ---------------------------------------------------------------------------------- */
+int64_t srh_au_ws_bytes(int64_t n, int32_t d);
+srh_status_t srh_au_chunk_plan(int64_t n, int64_t* chunks, int64_t* chunk_len);
+srh_status_t srh_au_fwd_bwd(const float* d_x, const float* d_y, int64_t n, int32_t d, float t, float w_align, float w_ux,
+                            float w_uy, double* d_parts, double* d_loss, float* d_gx, float* d_gy, void* d_ws,
+                            void* stream);
+
+/* ------------------------------------------------------------------------------------
  * (a-20) MHCN -- the self-gates, the channel attention and the hierarchical mutual-information loss of
  * model/graph/MHCN.py:79-93 and 159-181.  All arithmetic fp32; no float atomics: every reduction over rows runs in fixed
  * chunks whose partials are summed in chunk order, so a call returns the same bits every time.  d = 64 or 128 (zero-pad

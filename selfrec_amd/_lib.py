@@ -244,6 +244,9 @@ SIGNATURES = {
     "srh_mixup_fwd_f32": (_i32, [C.POINTER(MixupArgs), _vp, _vp, _vp, _vp, _vp]),
     "srh_mixup_bwd_ws_bytes": (_i64, [_i64, _i32]),
     "srh_mixup_bwd_f32": (_i32, [C.POINTER(MixupArgs), _vp, _vp, _vp, _vp, _vp]),
+    "srh_au_ws_bytes": (_i64, [_i64, _i32]),
+    "srh_au_chunk_plan": (_i32, [_i64, C.POINTER(_i64), C.POINTER(_i64)]),
+    "srh_au_fwd_bwd": (_i32, [_vp, _vp, _i64, _i32, _f32, _f32, _f32, _f32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "srh_adam_step": (_i32, [_vp, _vp, _vp, _vp, _i64, _i64, _vp, _f32, _f32, _f32, _f32, _vp]),
     "srh_adam_step_reset": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _vp, _f32, _f32, _f32, _f32, _vp, _i32, _vp, _vp, _vp]),
     "srh_score_mask_topk": (_i32, [_vp, _vp, _i64, _vp, _i64, _i32, _vp, _vp, _i32, _vp, _i64, _vp, _vp, _vp]),

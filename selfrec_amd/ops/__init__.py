@@ -5,6 +5,7 @@ and the current HIP stream to libselfrec_hip.so.  One submodule per kernel famil
 the package say ``ops.<name>`` (the layout and the rule for a new model's wrappers)."""
 from ._base import (NCE_WIDTHS, ROW_WIDTHS, SPMM_WIDTHS, TABLE_NCE_WIDTHS, LossGradFn, SelfrecHipError, SpmmEpilogue, _lib,
                     check, cut_cols, gpu_available, kernel_width, pad_cols, padded_width, require_gpu, to_width, u64, workspace)
+from .au import AlignUniformFn, au_fwd_bwd, au_supported
 from .contrastive import (KMEANS_MAX_POINTS_PER_CENTROID, KMEANS_SPLIT_EPS, BatchSoftmaxFn, InfoNceFn, TableCeFn,
                           batch_softmax_fwd_bwd, kmeans, kmeans_assign, kmeans_split, kmeans_update, table_ce_fwd_bwd,
                           table_nce_fwd_bwd, table_nce_ws)
@@ -42,5 +43,6 @@ __all__ = """
     seq_attn_fwd seq_attn_bwd seq_attn_full_fwd seq_attn_full_bwd SeqAttnFn SeqAttnFullFn seq_bce_fwd_bwd SeqBceFn
     GatherRowsFn seq_embed_supported seq_embed_fwd live_plan_host live_plan rows_live_sum SeqEmbedFn SeqBceLiveFn
     rows_l2norm_fwd rows_l2norm_bwd NormPropFn RowsL2NormFn tri_nd_fwd_bwd TriNdFn gate_fwd gate_bwd GateFn
-    chan_mix_fwd chan_mix_bwd ChanMixFn mim_fwd_bwd MimFn mixup_supported mixup_fwd mixup_bwd MixupFn
+    chan_mix_fwd chan_mix_bwd ChanMixFn mim_fwd_bwd MimFn mixup_supported mixup_fwd mixup_bwd MixupFn au_supported au_fwd_bwd
+    AlignUniformFn
 """.split()

@@ -11,6 +11,12 @@ forward and its backward on fixed hop tables (HIP events), one whole step (wall 
 of each.  Warm-up first; median, min and max of the repeats.
 
     python tools/oplevel_probe.py MixGCF --ab [--repeats 30] [--out profiles/mixgcf_probe.json]
+
+DirectAU's loss has two routes as well (``engine.au``: csrc/au.hip or the reference's expression over torch.pdist); its
+``--ab`` alternates them the same way at the conf's shape (B = 2048, 3 layers, d = 64): the loss forward on the two gathered
+blocks, its backward, the peak memory above the inputs, and one whole step.
+
+    python tools/oplevel_probe.py DirectAU --ab [--repeats 30] [--out profiles/directau_probe.json]
 """
 import sys
 import time
@@ -219,17 +225,109 @@ def probe_mixgcf_ab(repeats, out):
         json.dump(res, f, indent=1)
 
 
+def probe_directau_ab(repeats, out):
+    """DirectAU's loss on its two routes (``engine.au``: csrc/au.hip or the reference's torch expression over torch.pdist)
+    at the conf's shape, alternated in one process: the loss forward alone on two fixed gathered B x d blocks, its backward
+    alone (HIP events), the peak memory of forward + backward above the inputs, and one whole training step (wall time
+    between fences)."""
+    import json
+    import os
+    import random
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    from bert4rec_probe import peak_extra_bytes
+    from sept_probe import alternating, stats
+    from selfrec_amd import ops
+    from selfrec_amd.model.graph.DirectAU import DirectAU, alignment, uniformity
+    from selfrec_amd.util.sampler import next_batch_pairwise
+    ops.require_gpu()
+    B, L, d, gamma = 2048, 3, 64, 2.0
+    tu, ti, su, si, _, _ = synth.make_dataset("yelp2018")
+
+    def make(route):
+        conf = ModelConf({"training.set": "./none", "test.set": "./none", "model": {"name": "DirectAU", "type": "graph"},
+                          "item.ranking.topN": [10, 20], "embedding.size": d, "max.epoch": 1, "batch.size": B,
+                          "learning.rate": 0.001, "reg.lambda": 0.0001, "output": "./results/",
+                          "DirectAU": {"gamma": gamma, "n_layers": L}, "engine.au": route})
+        torch.manual_seed(0)
+        m = DirectAU(conf, synth.as_triples(tu, ti), synth.as_triples(su, si))
+        m.model.cuda().train()
+        assert m.au == route
+        return m
+    os.environ.pop("SRH_DIRECTAU_AU", None)
+    models = {r: make(r) for r in ("hip", "torch")}
+    base = models["hip"]
+    random.seed(1)
+    idx = [torch.from_numpy(a).cuda() for a in next(iter(next_batch_pairwise(base.data, B, 1, as_arrays=True)))]
+    user, pos, _ = idx
+    res = {"shape": {"dataset": "yelp2018 (synthetic)", "users": base.data.user_num, "items": base.data.item_num, "B": B,
+                     "n_layers": L, "d": d, "gamma": gamma, "t": 2}}
+
+    # ---- the loss alone, on the two gathered blocks ---------------------------------------------------------------------
+    with torch.no_grad():
+        users, items = base.model()
+        u0, p0 = users[user].contiguous(), items[pos].contiguous()
+
+    def forward(route):
+        u, p = u0.clone().requires_grad_(True), p0.clone().requires_grad_(True)
+        if route == "hip":
+            return ops.AlignUniformFn.apply(u, p, 2.0, 1.0, gamma / 2, gamma / 2)
+        return alignment(u, p) + gamma * (uniformity(u) + uniformity(p)) / 2
+    with torch.no_grad():
+        res["loss_value"] = {r: float(forward(r)) for r in ("hip", "torch")}
+    res["loss_fwd_ms"] = alternating({r: (lambda r=r: forward(r)) for r in ("hip", "torch")}, 5, repeats)
+    ts = {"hip": [], "torch": []}
+    for k in range(5 + repeats):
+        for r in ts:
+            loss = forward(r)
+            t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            t0.record()
+            loss.backward()
+            t1.record()
+            t1.synchronize()
+            if k >= 5:
+                ts[r].append(t0.elapsed_time(t1))
+    res["loss_bwd_ms"] = {r: stats(v) for r, v in ts.items()}
+    res["loss_peak_extra_bytes"] = {r: peak_extra_bytes(lambda r=r: forward(r).backward()) for r in ("hip", "torch")}
+
+    # ---- the whole step -------------------------------------------------------------------------------------------------
+    steps = {}
+    for name, m in models.items():
+        opt = torch.optim.Adam(m.model.parameters(), lr=1e-3)
+
+        def step(m=m, opt=opt):
+            loss = m.batch_loss(*idx)
+            opt.zero_grad()
+            loss.backward()
+            opt.step()
+        steps[name] = step
+    res["step_wall_ms"] = alternating(steps, 5, repeats, wall=True)
+    res["step_peak_extra_bytes"] = {name: peak_extra_bytes(fn) for name, fn in steps.items()}
+    med = lambda key, r: res[key][r]["median"]  # noqa: E731
+    res["hip_over_torch"] = {k: med(k, "hip") / med(k, "torch") for k in ("loss_fwd_ms", "loss_bwd_ms", "step_wall_ms")}
+    res["step_ranges_touch"] = not (res["step_wall_ms"]["hip"]["max"] < res["step_wall_ms"]["torch"]["min"]
+                                    or res["step_wall_ms"]["torch"]["max"] < res["step_wall_ms"]["hip"]["min"])
+    res["repeats"], res["warmup"] = repeats, 5
+    res["device"] = torch.cuda.get_device_name(0)
+    print(json.dumps(res, indent=1))
+    os.makedirs(os.path.dirname(out) or ".", exist_ok=True)
+    with open(out, "w") as f:
+        json.dump(res, f, indent=1)
+
+
 if __name__ == "__main__":
     if "--ab" in sys.argv:
         import argparse
         ap = argparse.ArgumentParser()
-        ap.add_argument("model", choices=["MixGCF"])
+        ap.add_argument("model", choices=["MixGCF", "DirectAU"])
         ap.add_argument("--ab", action="store_true")
         ap.add_argument("--repeats", type=int, default=30)
-        ap.add_argument("--out", default="profiles/mixgcf_probe.json")
+        ap.add_argument("--out", default=None)
         args = ap.parse_args()
         assert args.repeats >= 5
-        probe_mixgcf_ab(args.repeats, args.out)
+        if args.model == "DirectAU":
+            probe_directau_ab(args.repeats, args.out or "profiles/directau_probe.json")
+        else:
+            probe_mixgcf_ab(args.repeats, args.out or "profiles/mixgcf_probe.json")
         sys.exit(0)
     name = sys.argv[1] if len(sys.argv) > 1 else "BUIR"
     steps = int(sys.argv[2]) if len(sys.argv) > 2 else 40
