@@ -292,7 +292,9 @@ enum { SRH_SCALE_IN = 1, SRH_SCALE_OUT = 2 };
 /* y (n_rows, d) = A (CSR, fp32 values, int32 structure) * x (n_cols, d); d in {8,16,32,64,128,256}
  * (8 and 16: the thin-table kernel of the column-sharded layout).
  * x and y must not alias.  epi may be NULL.  d_vals may be NULL for d >= 64: A is then the PATTERN of the structure
- * (all stored entries 1) -- no value stream; column marks are not combined with it. */
+ * (all stored entries 1) -- no value stream; column marks are not combined with it.
+ * A structure with no stored entry (indptr all zero) is served: y is zero rows with the epilogue applied, d_indices and
+ * d_vals are never read and may be NULL (a zero-length device array has no address). */
 srh_status_t srh_spmm_f32(const srh_spmm_plan_t* plan, const int32_t* d_indptr,
                           const int32_t* d_indices, const float* d_vals, const float* d_x,
                           float* d_y, int32_t d, const srh_spmm_epilogue_t* epi, void* stream);
@@ -300,7 +302,8 @@ srh_status_t srh_spmm_f32(const srh_spmm_plan_t* plan, const int32_t* d_indptr,
 /* y_v = A_v x for three value arrays over ONE structure in one traversal (the x rows are gathered once):
  * the first layer of SGL.py:104-108, where the full adjacency and its two edge-dropped views
  * (data/augmentor.py:29-40: same indptr / indices, dropped entries = 0) multiply the same ego table.
- * Bit-identical to three srh_spmm_f32 calls.  d = 64 only (SRH_ERR_UNSUPPORTED otherwise). */
+ * Bit-identical to three srh_spmm_f32 calls, whatever the three arrays hold: an entry may be zero in any of them, the
+ * first included.  d = 64 only (SRH_ERR_UNSUPPORTED otherwise).  With no stored entry d_indices / d_vals* may be NULL. */
 srh_status_t srh_spmm3_f32(const srh_spmm_plan_t* plan, const int32_t* d_indices, const float* d_vals0,
                            const float* d_vals1, const float* d_vals2, const float* d_x, float* d_y0,
                            float* d_y1, float* d_y2, int32_t d, void* stream);

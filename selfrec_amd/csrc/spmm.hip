@@ -726,7 +726,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
 // dropped entries are zeros: data/augmentor.py:29-40) by the same ego table, so the x rows -- the
 // traffic that bounds this kernel -- are gathered once for all three.  Same schedule, DPP broadcasts
 // and in-kernel finish of split rows as spmm_rows_kernel; no epilogue (the layer has none).
+// The three arrays are independent: an entry's x row is gathered when any of its three values is
+// non-zero, so an array need not be a sub-graph of the first (the header: bit-identical to three calls).
 // ---------------------------------------------------------------------------------------------
+// c < 0: the entry issues no gather -- padding, or an entry that is zero in ALL THREE arrays (entry3 below)
 template <int LPR, int T0>
 __device__ __forceinline__ void gather8x3(int c, float v0, float v1, float v2, const float4* __restrict__ X, int sub,
                                           float4 (&acc)[3]) {
@@ -740,7 +743,7 @@ __device__ __forceinline__ void gather8x3(int c, float v0, float v1, float v2, c
 #pragma unroll
   for (int t = 0; t < 8; ++t) {
     xx[t] = f4_zero();
-    if (a0[t] != 0.f) xx[t] = ld_x<LPR>(X, cc[t], sub);     // (views are sub-graphs: a0 == 0 only for padding)
+    if (cc[t] >= 0) xx[t] = ld_x<LPR>(X, cc[t], sub);
   }
 #pragma unroll
   for (int t = 0; t < 8; ++t) {
@@ -775,6 +778,18 @@ __global__ __launch_bounds__(256) void spmm_rows3_kernel(const Task* __restrict_
   const int count = __builtin_amdgcn_readfirstlane(tk.count);
   float4 acc[3] = {f4_zero(), f4_zero(), f4_zero()};
   float4* const Y[3] = {Y0, Y1, Y2};
+  // entry j of the three arrays, zeros past `end`.  The x row is gathered when ANY of the three values is non-zero (the
+  // arrays need not be sub-graphs of the first one); the test is made here, once per entry, and travels with the column
+  // as its sign: gather8x3 pays one compare per broadcast entry, as it did when it looked at the first value alone.
+  auto entry3 = [&](int j, int end, int& c, float& v0, float& v1, float& v2) {
+    c = -1;
+    v0 = v1 = v2 = 0.f;
+    if (j < end) {
+      const int cj = indices[j];                           // (issued with the values, not behind them)
+      v0 = vals0[j]; v1 = vals1[j]; v2 = vals2[j];
+      if (v0 != 0.f || v1 != 0.f || v2 != 0.f) c = cj;
+    }
+  };
 
   if (kind == 0) {
     const Seg sg = segs[first];
@@ -782,9 +797,9 @@ __global__ __launch_bounds__(256) void spmm_rows3_kernel(const Task* __restrict_
     const int e = __builtin_amdgcn_readfirstlane(sg.end), slot = __builtin_amdgcn_readfirstlane(sg.slot);
     for (int base = s; base < e; base += CH) {
       const int j = base + G * e16 + g;                  // (dealt round-robin to the groups, as spmm_rows_kernel does)
-      int c = 0;
-      float v0 = 0.f, v1 = 0.f, v2 = 0.f;
-      if (j < e) { c = indices[j]; v0 = vals0[j]; v1 = vals1[j]; v2 = vals2[j]; }
+      int c;
+      float v0, v1, v2;
+      entry3(j, e, c, v0, v1, v2);
       gather8x3<LPR, 0>(c, v0, v1, v2, X, sub, acc);
       if (e - base > 8) gather8x3<LPR, 8>(c, v0, v1, v2, X, sub, acc);
     }
@@ -822,9 +837,9 @@ __global__ __launch_bounds__(256) void spmm_rows3_kernel(const Task* __restrict_
   maxlen = __builtin_amdgcn_readfirstlane(maxlen);
   for (int q = 0; q * 16 < maxlen; ++q) {
     const int j = s + 16 * q + e16;
-    int c = 0;
-    float v0 = 0.f, v1 = 0.f, v2 = 0.f;
-    if (j < e) { c = indices[j]; v0 = vals0[j]; v1 = vals1[j]; v2 = vals2[j]; }
+    int c;
+    float v0, v1, v2;
+    entry3(j, e, c, v0, v1, v2);
     gather8x3<LPR, 0>(c, v0, v1, v2, X, sub, acc);
     if (maxlen - 16 * q > 8) gather8x3<LPR, 8>(c, v0, v1, v2, X, sub, acc);
   }
@@ -1415,6 +1430,12 @@ static srh_status_t spmm_launch(const srh_spmm_plan_t* plan, const int32_t* d_in
     if (srh_status_t rc = srh::check_fetch_args(fetch, fetch_args)) return rc;
     n_fetch = srh::kFetchBlocks;
   }
+  // A structure with no stored entry: no kernel reads an entry, and a zero-length device array may have no address at
+  // all -- the index and value streams get a stand-in one (the product is zero rows plus the epilogue, pattern or not).
+  if (plan && plan->nnz == 0) {
+    if (!d_indices) d_indices = reinterpret_cast<const int32_t*>(plan->d_tsegs);
+    if (!d_vals) d_vals = reinterpret_cast<const float*>(plan->d_tsegs);
+  }
   SRH_REQUIRE(plan && d_indices && d_x && d_y, "spmm_f32: null argument");
   SRH_REQUIRE(d_vals || (d >= 64 && !(epi && epi->d_col_mark)),
               "spmm_f32: a pattern matrix (d_vals == NULL) needs d >= 64 and no column marks");
@@ -1640,6 +1661,13 @@ void srh_spmm_plan_destroy(srh_spmm_plan_t* p) {
 srh_status_t srh_spmm3_f32(const srh_spmm_plan_t* plan, const int32_t* d_indices, const float* d_vals0,
                            const float* d_vals1, const float* d_vals2, const float* d_x, float* d_y0,
                            float* d_y1, float* d_y2, int32_t d, void* stream) {
+  if (plan && plan->nnz == 0) {              // no stored entry: nothing is read through these (see spmm_launch)
+    const void* const stand_in = plan->d_tsegs;
+    if (!d_indices) d_indices = static_cast<const int32_t*>(stand_in);
+    if (!d_vals0) d_vals0 = static_cast<const float*>(stand_in);
+    if (!d_vals1) d_vals1 = static_cast<const float*>(stand_in);
+    if (!d_vals2) d_vals2 = static_cast<const float*>(stand_in);
+  }
   SRH_REQUIRE(plan && d_indices && d_vals0 && d_vals1 && d_vals2 && d_x && d_y0 && d_y1 && d_y2, "spmm3_f32: null argument");
   SRH_REQUIRE(d_x != d_y0 && d_x != d_y1 && d_x != d_y2 && d_y0 != d_y1 && d_y0 != d_y2 && d_y1 != d_y2,
               "spmm3_f32: x and the three outputs must be distinct");

@@ -204,7 +204,8 @@ def adam_inputs(m, d, seed):
     empty = np.diff(m.indptr) == 0
     add_live = rng.random(n) < 0.3
     add_live[empty] = False
-    s = dict(x=f(1e-3), add=[f(1e-2), f(1e-2)], m=f(1e-3), v=(rng.random((n, d)) * 1e-5).astype(np.float32),
+    x = (rng.standard_normal((m.shape[1], d)) * 1e-3).astype(np.float32)      # (n_cols rows: the matrix may be rectangular)
+    s = dict(x=x, add=[f(1e-2), f(1e-2)], m=f(1e-3), v=(rng.random((n, d)) * 1e-5).astype(np.float32),
              p=(rng.uniform(0.05, 0.15, (n, d)) * rng.choice([-1.0, 1.0], (n, d))).astype(np.float32),
              r=row_scale_with_zeros(m), add_live=add_live, empty=empty)
     for t in s["add"] + [s["m"], s["v"]]:
