@@ -1171,6 +1171,68 @@ srh_status_t srh_au_fwd_bwd(const float* d_x, const float* d_y, int64_t n, int32
                             void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * (a-23) Bootstrap losses -- BUIR (model/graph/BUIR.py:69-95) and SelfCF (model/graph/SelfCF.py:64-91): the predictor,
+ * the two cosine terms against momentum-mixed targets, every gradient and the history store in one call; and BUIR's
+ * momentum update of the batch's target rows.  All arithmetic fp32, loss and parts leave as doubles, no float atomics.
+ * Online rows x_u, x_i (B x d float32, row-major), predictor p(x) = W x + b (nn.Linear: d_w is d x d, out x in), and per
+ * side a target table T_side of n_tgt rows read at d_idx[r] (d_idx == NULL: B rows, read at r):
+ *     t_side[r] = alpha T_side[idx_side[r]] + beta x_side[r]      (fl(fl(alpha T) + fl(beta x)); no gradient flows through it)
+ *     vh = v / max(|v|, eps),   cu_r = ph(x_u[r]) . th(t_i[r]),   ci_r = ph(x_i[r]) . th(t_u[r])
+ *     loss = c0 - c1 (mean_r cu_r + mean_r ci_r)
+ *   BUIR: alpha = 1, beta = 0, eps = 1e-12 (F.normalize), c0 = 4, c1 = 2, clamp = SRH_BOOT_CLAMP_NORMALIZE, T = the target
+ *   encoder's propagated tables.
+ *   SelfCF: alpha = m, beta = 1 - m, eps = 1e-8 (F.cosine_similarity: each side over max(norm, eps)), c0 = 1, c1 = 0.5,
+ *   clamp = SRH_BOOT_CLAMP_COSINE, T = the history tables, which are also d_store.
+ *   Gradients in closed form: dP_r = -(c1 / B) (th - (ph . th) ph) / |p| on an ordinary row;  dX = dP W;
+ *   d_gw = dP_u^T X_u + dP_i^T X_i;  d_gb = the column sums of both dP.  Where |p| was clamped the two forward-equal
+ *   expressions differentiate differently, and `clamp` says which one the caller's model is:
+ *     SRH_BOOT_CLAMP_NORMALIZE  dP_r = -(c1 / B) th / eps, no projection: autograd through x / max(|x|, eps)
+ *     SRH_BOOT_CLAMP_COSINE     dP_r = -(c1 / B) (th - (ph . th) p / |p|) / eps (p / |p| = 0 at p = 0): F.cosine_similarity
+ *                               clamps the norm in place outside the graph, so the norm's own derivative stays
+ * srh_boot_fwd_bwd WRITES, by plain stores, every element of user->d_gx and item->d_gx (B x d), d_gw (d x d), d_gb (d),
+ *   d_parts[0..1] = mean cu, mean ci and d_loss[0] (doubles on the device); then, where a side's d_store is given (a table
+ *   of n_tgt rows, which may be that side's d_tgt), d_store[d_idx[r]] = x[r] for every slot.  Every target read of the call
+ *   happens before any of these stores (they are the last launch): a slot never sees a history row that another slot of the
+ *   same call has overwritten -- torch's gather, then index-assign.  Slots of one id are expected to hold the same x row
+ *   (rows gathered by that id), so their stores are the same bits.  An id outside [0, n_tgt) reads a zero row and its
+ *   store is skipped, as in srh_tower_fwd_f32; its gradients are still per slot.  Neither the outputs nor the workspace
+ *   need any initialisation by the caller, and a call returns the same bits every time.
+ * Launches: main (side x 64-row tile, 16 rows per wave, on v_mfma_f32_16x16x4_f32: the tile's rows in registers, W
+ *   streamed through LDS 64 output rows at a time, P^T = W X^T + b on the accumulator; target mix, norms and the cosine in
+ *   the accumulator's layout; dP formed there, written for the weight gradients and fed back as the B operand of
+ *   dX^T = W^T dP^T), the loss (row terms of each side in one fixed order), the weight gradients (dP^T X and the column
+ *   sums per chunk of 256 rows; the chunk partials summed in chunk order, the user side before the item side), the store.
+ * Envelope: d = 64 or 128 (zero-pad narrower rows TOGETHER WITH the rows and columns of W and the entries of b: a padded
+ *   column changes no result and takes exactly zero gradient), else SRH_ERR_UNSUPPORTED with a message; 1 <= B < 2^24;
+ *   alpha, beta, c0, c1 finite; eps > 0; clamp one of the two above.  All arguments are checked before any launch.  d_ws >= srh_boot_ws_bytes(B, d)
+ *   (0 for a shape the kernels do not serve): 2 B d floats, 2 B doubles and per side and chunk d x d + d floats.
+ *
+ * srh_rows_momentum_f32 (BUIR.py:69-75, update_target): tgt[idx] = tgt[idx] * m + src[idx] * (1 - m) for the n slots of
+ *   d_idx (int32) over two tables of n_table rows x d.  Phase 1 computes fl(fl(tgt[id] m) + fl(src[id] one_minus_m)) for
+ *   every slot from the values the table held BEFORE the call (no contraction into a fused multiply-add), phase 2, a launch
+ *   of its own, stores them: slots of one id compute and store the same bits, so a repeated id is updated once, as torch's
+ *   index assignment does.  An id outside [0, n_table) is skipped.  Any d >= 1, n >= 0; the caller passes m and 1 - m as
+ *   the two floats torch rounds them to.  d_ws >= srh_rows_momentum_ws_bytes(n, d) = n d floats (0 for n < 1 or d < 1).
+ * ---------------------------------------------------------------------------------- */
+#define SRH_BOOT_CLAMP_NORMALIZE 0
+#define SRH_BOOT_CLAMP_COSINE 1
+typedef struct srh_boot_side {
+  const float* d_x;       /* B x d, read */
+  const float* d_tgt;     /* n_tgt x d (B x d when d_idx is NULL), read */
+  const int32_t* d_idx;   /* B, or NULL */
+  int64_t n_tgt;
+  float* d_store;         /* n_tgt x d, or NULL; may be d_tgt */
+  float* d_gx;            /* B x d, written */
+} srh_boot_side_t;
+int64_t srh_boot_ws_bytes(int64_t B, int32_t d);
+srh_status_t srh_boot_fwd_bwd(const srh_boot_side_t* user, const srh_boot_side_t* item, const float* d_w, const float* d_b,
+                              int64_t B, int32_t d, float alpha, float beta, float eps, float c0, float c1, int32_t clamp,
+                              double* d_parts, double* d_loss, float* d_gw, float* d_gb, void* d_ws, void* stream);
+int64_t srh_rows_momentum_ws_bytes(int64_t n, int32_t d);
+srh_status_t srh_rows_momentum_f32(float* d_tgt, const float* d_src, const int32_t* d_idx, int64_t n, int64_t n_table,
+                                   int32_t d, float m, float one_minus_m, void* d_ws, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * (a-20) MHCN -- the self-gates, the channel attention and the hierarchical mutual-information loss of
  * model/graph/MHCN.py:79-93 and 159-181.  All arithmetic fp32; no float atomics: every reduction over rows runs in fixed
  * chunks whose partials are summed in chunk order, so a call returns the same bits every time.  d = 64 or 128 (zero-pad

@@ -85,6 +85,7 @@ class MimArgs(C.Structure):
 
 
 SRH_MIXUP_MAX_HOPS = 8
+SRH_BOOT_CLAMP_NORMALIZE, SRH_BOOT_CLAMP_COSINE = 0, 1
 
 
 class MixupArgs(C.Structure):
@@ -93,6 +94,12 @@ class MixupArgs(C.Structure):
                 ("d_grad", C.c_void_p * SRH_MIXUP_MAX_HOPS), ("d_pos", C.c_void_p), ("d_neg", C.c_void_p),
                 ("n_items", C.c_int64), ("B", C.c_int64), ("n_hops", C.c_int32), ("n_negs", C.c_int32), ("d", C.c_int32),
                 ("rng_seed", C.c_uint64), ("rng_counter", C.c_uint64)]
+
+
+class BootSide(C.Structure):
+    """struct srh_boot_side (include/selfrec_hip.h)."""
+    _fields_ = [("d_x", C.c_void_p), ("d_tgt", C.c_void_p), ("d_idx", C.c_void_p), ("n_tgt", C.c_int64),
+                ("d_store", C.c_void_p), ("d_gx", C.c_void_p)]
 
 
 SCALAR_WS_BYTES = 64        # SRH_SCALAR_WS_BYTES
@@ -247,6 +254,11 @@ SIGNATURES = {
     "srh_au_ws_bytes": (_i64, [_i64, _i32]),
     "srh_au_chunk_plan": (_i32, [_i64, C.POINTER(_i64), C.POINTER(_i64)]),
     "srh_au_fwd_bwd": (_i32, [_vp, _vp, _i64, _i32, _f32, _f32, _f32, _f32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "srh_boot_ws_bytes": (_i64, [_i64, _i32]),
+    "srh_boot_fwd_bwd": (_i32, [C.POINTER(BootSide), C.POINTER(BootSide), _vp, _vp, _i64, _i32, _f32, _f32, _f32, _f32, _f32,
+                                _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "srh_rows_momentum_ws_bytes": (_i64, [_i64, _i32]),
+    "srh_rows_momentum_f32": (_i32, [_vp, _vp, _vp, _i64, _i64, _i32, _f32, _f32, _vp, _vp]),
     "srh_adam_step": (_i32, [_vp, _vp, _vp, _vp, _i64, _i64, _vp, _f32, _f32, _f32, _f32, _vp]),
     "srh_adam_step_reset": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _vp, _f32, _f32, _f32, _f32, _vp, _i32, _vp, _vp, _vp]),
     "srh_score_mask_topk": (_i32, [_vp, _vp, _i64, _vp, _i64, _i32, _vp, _vp, _i32, _vp, _i64, _vp, _vp, _vp]),

@@ -1,12 +1,19 @@
 """SelfCF-he (Zhou et al.; reference model/graph/SelfCF.py:13-91), op-level tier: one LightGCN encoder, a linear
 predictor, and target vectors taken from the previous visit of each user / item (history embeddings) mixed with
-the current ones -- no negatives, no second encoder.  Config block ``SelfCF: {n_layer, tau}``."""
+the current ones -- no negatives, no second encoder.  Config block ``SelfCF: {n_layer, tau}``.
+
+The model-specific part has two routes, ``engine.boot`` / ``SRH_BOOT``: ``hip`` is ops.BootstrapLossFn
+(csrc/bootstrap.hip: the momentum mix with the history rows, the predictor, both cosine terms, every gradient and the
+history store in one call -- every history row is read before any is overwritten); ``torch`` is the reference's
+expression, its A/B partner in tools/oplevel_probe.py.  An embedding wider than the kernels serve takes the torch
+expression on either route."""
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from ... import ops
 from ._oplevel import PropagationEncoder
-from .BUIR import _TwoTowerScores
+from .BUIR import _TwoTowerScores, boot_route
 
 
 class SelfCF_HE(nn.Module):
@@ -31,6 +38,15 @@ class SelfCF_HE(nn.Module):
             self.i_target_his[items, :] = i_now.data.clone()
         return self.predictor(u_now), u_target, self.predictor(i_now), i_target
 
+    def bootstrap_loss(self, inputs):
+        """forward() and get_loss() as one kernel call; the history tables are read, then written, inside it"""
+        u_all, i_all = self.online_encoder()
+        users, items = inputs['user'], inputs['item']
+        m = self.momentum
+        return ops.BootstrapLossFn.apply(u_all[users], i_all[items], self.predictor.weight, self.predictor.bias,
+                                         self.u_target_his, self.i_target_his, users, items, self.u_target_his,
+                                         self.i_target_his, m, 1. - m, 1e-8, 1.0, 0.5, True)
+
     @torch.no_grad()
     def get_embedding(self):
         u, i = self.online_encoder()
@@ -50,7 +66,10 @@ class SelfCF(_TwoTowerScores):
         super().__init__(conf, training_set, test_set)
         block = self.config['SelfCF']
         self.momentum, self.n_layers = float(block['tau']), int(block['n_layer'])
+        self.boot = boot_route(self.config, 'SelfCF')
         self.model = SelfCF_HE(self.data, self.emb_size, self.momentum, self.n_layers)
 
     def batch_loss(self, user_idx, pos_idx, neg_idx):
+        if self.boot == 'hip' and ops.boot_supported(self.emb_size):
+            return self.model.bootstrap_loss({'user': user_idx, 'item': pos_idx})
         return self.model.get_loss(self.model({'user': user_idx, 'item': pos_idx}))

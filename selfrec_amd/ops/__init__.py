@@ -6,6 +6,7 @@ the package say ``ops.<name>`` (the layout and the rule for a new
 from ._base import (NCE_WIDTHS, ROW_WIDTHS, SPMM_WIDTHS, TABLE_NCE_WIDTHS, LossGradFn, SelfrecHipError, SpmmEpilogue, _lib,
                     check, cut_cols, gpu_available, kernel_width, pad_cols, padded_width, require_gpu, to_width, u64, workspace)
 from .au import AlignUniformFn, au_fwd_bwd, au_supported
+from .boot import BootstrapLossFn, boot_fwd_bwd, boot_supported, rows_momentum
 from .contrastive import (KMEANS_MAX_POINTS_PER_CENTROID, KMEANS_SPLIT_EPS, BatchSoftmaxFn, InfoNceFn, TableCeFn,
                           batch_softmax_fwd_bwd, kmeans, kmeans_assign, kmeans_split, kmeans_update, table_ce_fwd_bwd,
                           table_nce_fwd_bwd, table_nce_ws)
@@ -44,5 +45,5 @@ __all__ = """
     GatherRowsFn seq_embed_supported seq_embed_fwd live_plan_host live_plan rows_live_sum SeqEmbedFn SeqBceLiveFn
     rows_l2norm_fwd rows_l2norm_bwd NormPropFn RowsL2NormFn tri_nd_fwd_bwd TriNdFn gate_fwd gate_bwd GateFn
     chan_mix_fwd chan_mix_bwd ChanMixFn mim_fwd_bwd MimFn mixup_supported mixup_fwd mixup_bwd MixupFn au_supported au_fwd_bwd
-    AlignUniformFn
+    AlignUniformFn boot_supported boot_fwd_bwd BootstrapLossFn rows_momentum
 """.split()

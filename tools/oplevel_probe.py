@@ -17,6 +17,14 @@ DirectAU's loss has two routes as well (``engine.au``: csrc/au.hip or the refere
 blocks, its backward, the peak memory above the inputs, and one whole step.
 
     python tools/oplevel_probe.py DirectAU --ab [--repeats 30] [--out profiles/directau_probe.json]
+
+BUIR and SelfCF share the bootstrap route (``engine.boot``: csrc/bootstrap.hip or the reference's torch expressions); their
+``--ab`` alternates the routes at the conf's shape (B = 2048, 2 layers, d = 64): the model-specific piece -- target gather or
+momentum mix, predictor, loss, backward, history store -- forward plus backward on prepared inputs, BUIR's ``update_target``
+alone, the peak memory of the piece above its inputs, and one whole step.  Each model writes its own key of the file.
+
+    python tools/oplevel_probe.py BUIR --ab [--repeats 30] [--out profiles/boot_probe.json]
+    python tools/oplevel_probe.py SelfCF --ab
 """
 import sys
 import time
@@ -314,17 +322,131 @@ def probe_directau_ab(repeats, out):
         json.dump(res, f, indent=1)
 
 
+def probe_boot_ab(name, repeats, out):
+    """BUIR's or SelfCF's model-specific piece on its two routes (``engine.boot``), alternated in one process: the piece
+    forward + backward on prepared inputs (HIP events), BUIR's update_target alone, the peak memory of the piece above its
+    inputs, and one whole training step with its after_step (wall time between fences)."""
+    import importlib
+    import json
+    import os
+    import random
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    from bert4rec_probe import peak_extra_bytes
+    from sept_probe import alternating
+    from selfrec_amd import ops
+    from selfrec_amd.util.sampler import next_batch_pairwise
+    ops.require_gpu()
+    B, L, d = 2048, 2, 64
+    block = {"BUIR": {"n_layer": L, "tau": 0.995, "drop_rate": 0.2}, "SelfCF": {"n_layer": L, "tau": 0.05}}[name]
+    tu, ti, su, si, _, _ = synth.make_dataset("yelp2018")
+    cls = getattr(importlib.import_module(f"selfrec_amd.model.graph.{name}"), name)
+
+    def make(route):
+        conf = ModelConf({"training.set": "./none", "test.set": "./none", "model": {"name": name, "type": "graph"},
+                          "item.ranking.topN": [10, 20], "embedding.size": d, "max.epoch": 1, "batch.size": B,
+                          "learning.rate": 0.001, "reg.lambda": 0.0001, "output": "./results/", name: block,
+                          "engine.boot": route})
+        torch.manual_seed(0)
+        m = cls(conf, synth.as_triples(tu, ti), synth.as_triples(su, si))
+        m.model.cuda().train()
+        assert m.boot == route
+        return m
+    os.environ.pop("SRH_BOOT", None)
+    models = {r: make(r) for r in ("hip", "torch")}
+    base = models["hip"].model
+    random.seed(1)
+    idx = [torch.from_numpy(a).cuda() for a in next(iter(next_batch_pairwise(models["hip"].data, B, 1, as_arrays=True)))]
+    user, pos, _ = idx
+    u32, p32 = user.to(torch.int32), pos.to(torch.int32)
+    res = {"shape": {"dataset": "yelp2018 (synthetic)", "users": models["hip"].data.user_num,
+                     "items": models["hip"].data.item_num, "B": B, "n_layer": L, "d": d, **block}}
+
+    # ---- the model-specific piece alone, on prepared inputs ---------------------------------------------------------------
+    W, b = base.predictor.weight, base.predictor.bias
+    with torch.no_grad():
+        on = base.online_encoder
+        u_all, i_all = super(type(on), on).forward() if name == "BUIR" else on()        # (BUIR: the tables without dropout)
+        u0, i0 = u_all[user].contiguous(), i_all[pos].contiguous()
+        if name == "BUIR":
+            t_u, t_i = (t.contiguous() for t in super(type(base.target_encoder), base.target_encoder).forward())
+        else:
+            his = {r: (base.u_target_his.clone(), base.i_target_his.clone()) for r in ("hip", "torch")}
+    mom = getattr(base, "momentum", None)
+
+    def piece(route):
+        u, i = u0.clone().requires_grad_(True), i0.clone().requires_grad_(True)
+        W.grad = b.grad = None
+        if name == "BUIR":
+            if route == "hip":
+                loss = ops.BootstrapLossFn.apply(u, i, W, b, t_u, t_i, u32, p32, None, None, 1.0, 0.0, 1e-12, 4.0, 2.0)
+            else:
+                loss = base.get_loss((base.predictor(u), t_u[user], base.predictor(i), t_i[pos]))
+        else:
+            hu, hi = his[route]
+            if route == "hip":
+                loss = ops.BootstrapLossFn.apply(u, i, W, b, hu, hi, user, pos, hu, hi, mom, 1. - mom, 1e-8, 1.0, 0.5, True)
+            else:
+                with torch.no_grad():
+                    u_target = hu[user] * mom + u.data * (1. - mom)
+                    i_target = hi[pos] * mom + i.data * (1. - mom)
+                    hu[user, :] = u.data.clone()
+                    hi[pos, :] = i.data.clone()
+                loss = base.get_loss((base.predictor(u), u_target, base.predictor(i), i_target))
+        loss.backward()
+        return loss
+    res["piece_loss_value"] = {r: float(piece(r)) for r in ("hip", "torch")}
+    res["piece_fwd_bwd_ms"] = alternating({r: (lambda r=r: piece(r)) for r in ("hip", "torch")}, 5, repeats)
+    res["piece_peak_extra_bytes"] = {r: peak_extra_bytes(lambda r=r: piece(r)) for r in ("hip", "torch")}
+    keys = ["piece_fwd_bwd_ms", "step_wall_ms"]
+    if name == "BUIR":
+        upd = {"hip": lambda: base.update_target_rows(u32, p32), "torch": lambda: base.update_target(user, pos)}
+        res["update_target_ms"] = alternating(upd, 5, repeats)
+        keys.insert(1, "update_target_ms")
+
+    # ---- the whole step ---------------------------------------------------------------------------------------------------
+    steps = {}
+    for route, m in models.items():
+        opt = torch.optim.Adam([p for p in m.model.parameters() if p.requires_grad], lr=1e-3)
+
+        def step(m=m, opt=opt):
+            loss = m.batch_loss(*idx)
+            opt.zero_grad()
+            loss.backward()
+            opt.step()
+            m.after_step(*idx)
+        steps[route] = step
+    res["step_wall_ms"] = alternating(steps, 5, repeats, wall=True)
+    res["step_peak_extra_bytes"] = {route: peak_extra_bytes(fn) for route, fn in steps.items()}
+    med = lambda key, r: res[key][r]["median"]  # noqa: E731
+    res["hip_over_torch"] = {k: med(k, "hip") / med(k, "torch") for k in keys}
+    res["step_ranges_touch"] = not (res["step_wall_ms"]["hip"]["max"] < res["step_wall_ms"]["torch"]["min"]
+                                    or res["step_wall_ms"]["torch"]["max"] < res["step_wall_ms"]["hip"]["min"])
+    res["repeats"], res["warmup"] = repeats, 5
+    res["device"] = torch.cuda.get_device_name(0)
+    print(json.dumps(res, indent=1))
+    os.makedirs(os.path.dirname(out) or ".", exist_ok=True)
+    whole = {}
+    if os.path.exists(out):
+        with open(out) as f:
+            whole = json.load(f)
+    whole[name] = res
+    with open(out, "w") as f:
+        json.dump(whole, f, indent=1, sort_keys=True)
+
+
 if __name__ == "__main__":
     if "--ab" in sys.argv:
         import argparse
         ap = argparse.ArgumentParser()
-        ap.add_argument("model", choices=["MixGCF", "DirectAU"])
+        ap.add_argument("model", choices=["MixGCF", "DirectAU", "BUIR", "SelfCF"])
         ap.add_argument("--ab", action="store_true")
         ap.add_argument("--repeats", type=int, default=30)
         ap.add_argument("--out", default=None)
         args = ap.parse_args()
         assert args.repeats >= 5
-        if args.model == "DirectAU":
+        if args.model in ("BUIR", "SelfCF"):
+            probe_boot_ab(args.model, args.repeats, args.out or "profiles/boot_probe.json")
+        elif args.model == "DirectAU":
             probe_directau_ab(args.repeats, args.out or "profiles/directau_probe.json")
         else:
             probe_mixgcf_ab(args.repeats, args.out or "profiles/mixgcf_probe.json")
