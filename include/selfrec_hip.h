@@ -1233,6 +1233,48 @@ srh_status_t srh_rows_momentum_f32(float* d_tgt, const float* d_src, const int32
                                    int32_t d, float m, float one_minus_m, void* d_ws, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * (a-24) The rest of util/loss_torch.py -- info_nce (:54-88), InfoNCE with b_cos=False or a low temperature (:35-50),
+ * triplet_loss (:12-16) and kl_divergence (:91-94).  DESIGN.md 4.27.
+ *
+ * srh_pair_ce_fwd_bwd: srh_table_ce_fwd_bwd of (a-17) -- the same kernels, ownership, chunking, workspace layout
+ *   (srh_pair_ce_ws_bytes(M, N, d) == srh_table_ce_ws_bytes(M, N, d)), repeatability and label rule -- with scaled logits
+ *   s_mj = inv_temp * h_m . t_j and, with exclude_diagonal != 0 (M == N), key j = m left out of row m's softmax:
+ *     d_loss[0] = loss_scale * sum_m (lse_m - s_{m, label_m}),  lse_m = log sum_{j (!= m)} exp(s_mj)
+ *     d_gh (M x d) = loss_scale * inv_temp * (sum_j P_mj t_j - t_{label_m}),  P_mj = exp(s_mj - lse_m) (0 at j = m if excluded)
+ *     d_gt (N x d) = loss_scale * inv_temp * sum_m (P_mj - [j == label_m]) h_m
+ *   add_gh_into_gt != 0 (M == N): d_gt receives d_gt + d_gh row by row (d_gh is written as above); a caller whose H and T
+ *   are one matrix z reads dL/dz from d_gt.  d_h and d_t may be the same address (both are only read); d_gh and d_gt
+ *   may not.  Under exclusion a row can meet a key tile or chunk that holds no key but its own: it contributes nothing.
+ *   labels[m] == m under exclusion names a key that is not in the row's softmax: that row's loss term is NaN, as for a
+ *   label outside [0, N) (same gradient rule: the row has no one-hot).  exclude_diagonal with N == 1 or M != N,
+ *   add_gh_into_gt with M != N, inv_temp not positive and finite, a non-finite loss_scale: SRH_ERR_INVALID_ARG with a
+ *   message, before any launch.  d = 64 or 128.
+ *   InfoNCE(v1, v2, tau, b_cos=False): labels = 0..n-1, inv_temp = 1/tau, loss_scale = 1/n.  info_nce(z_i, z_j, temp, B):
+ *   H = T = cat(z_i, z_j), labels[m] = (m + B) mod 2B, inv_temp = 1/temp, loss_scale = 1/(2B), both flags set.
+ * srh_triplet_fwd_bwd: x_b = |u_b - p_b|^2 - |u_b - n_b|^2 + margin over B rows of d columns (32, 64, 128 or 256):
+ *     d_loss[0] = mean_b max(x_b, 0) (double);  rows with x_b > 0: d_gu = 2 (n - p) / B, d_gp = -2 (u - p) / B,
+ *     d_gn = 2 (u - n) / B;  rows with x_b <= 0: exact zeros.  All four WRITTEN; the three gradient buffers are distinct.
+ *   The distances are summed in double; the mean is taken on the device in a fixed order (no float atomics).
+ *   d_ws >= srh_triplet_ws_bytes(B), any content.
+ * srh_kl_div_fwd_bwd: rows of R x C logits, any R >= 1, C >= 1 (C is a loop bound, nothing is padded):
+ *     p = softmax(p_logit_r), q = softmax(q_logit_r), kl_r = sum_c p_c (log p_c - log q_c);  d_loss[0] = mean_r kl_r (double)
+ *     d_gp (R x C) = p_rc ((log p_rc - log q_rc) - kl_r) / R,   d_gq (R x C) = (q_rc - p_rc) / R
+ *   Both softmaxes max-subtracted; a column with p_c == 0 contributes 0.  d_p_logit may equal d_q_logit (loss 0); d_gp and
+ *   d_gq are distinct.  d_ws >= srh_kl_div_ws_bytes(R), any content.
+ * ---------------------------------------------------------------------------------- */
+int64_t srh_pair_ce_ws_bytes(int64_t M, int64_t N, int32_t d);
+srh_status_t srh_pair_ce_fwd_bwd(const float* d_h, int64_t M, const float* d_t, int64_t N, int32_t d,
+                                 const int32_t* d_labels, float inv_temp, float loss_scale, int32_t exclude_diagonal,
+                                 int32_t add_gh_into_gt, double* d_loss, float* d_gh, float* d_gt, void* d_ws,
+                                 void* stream);
+int64_t srh_triplet_ws_bytes(int64_t B);
+srh_status_t srh_triplet_fwd_bwd(const float* d_u, const float* d_p, const float* d_n, int64_t B, int32_t d, float margin,
+                                 double* d_loss, float* d_gu, float* d_gp, float* d_gn, void* d_ws, void* stream);
+int64_t srh_kl_div_ws_bytes(int64_t R);
+srh_status_t srh_kl_div_fwd_bwd(const float* d_p_logit, const float* d_q_logit, int64_t R, int64_t C, double* d_loss,
+                                float* d_gp, float* d_gq, void* d_ws, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * (a-20) MHCN -- the self-gates, the channel attention and the hierarchical mutual-information loss of
  * model/graph/MHCN.py:79-93 and 159-181.  All arithmetic fp32; no float atomics: every reduction over rows runs in fixed
  * chunks whose partials are summed in chunk order, so a call returns the same bits every time.  d = 64 or 128 (zero-pad

@@ -231,6 +231,12 @@ SIGNATURES = {
                                          _vp, _vp]),
     "srh_table_ce_ws_bytes": (_i64, [_i64, _i64, _i32]),
     "srh_table_ce_fwd_bwd": (_i32, [_vp, _i64, _vp, _i64, _i32, _vp, _f32, _vp, _vp, _vp, _vp, _vp]),
+    "srh_pair_ce_ws_bytes": (_i64, [_i64, _i64, _i32]),
+    "srh_pair_ce_fwd_bwd": (_i32, [_vp, _i64, _vp, _i64, _i32, _vp, _f32, _f32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "srh_triplet_ws_bytes": (_i64, [_i64]),
+    "srh_triplet_fwd_bwd": (_i32, [_vp, _vp, _vp, _i64, _i32, _f32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "srh_kl_div_ws_bytes": (_i64, [_i64]),
+    "srh_kl_div_fwd_bwd": (_i32, [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp]),
     "srh_seq_bce_ws_bytes": (_i64, [_i64]),
     "srh_seq_bce_fwd_bwd": (_i32, [_vp, _i64, _i32, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
     "srh_seq_embed_fwd_f32": (_i32, [_vp, _i64, _vp, _i64, _vp, _vp, _i64, _i32, _f32, _vp, _u64, _u64, _f32, _vp, _vp]),

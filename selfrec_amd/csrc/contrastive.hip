@@ -40,6 +40,13 @@
 // row's largest chunk max, merges the partials in chunk order with exp(max_c - max), and fixes lse_m; pass 2 weighs with
 // exp(s - lse_m) - [j == label_m] <= 1 and sums each 64-row tile from zero before adding it to the key's total (DESIGN.md
 // 4.20).  No prep launch: the rows are used as they are.
+//
+// The pair cross-entropy (srh_pair_ce_fwd_bwd, util/loss_torch.py:35-50 with b_cos=False and :54-88) is
+// the same three kernels under the PAIR template flag: the logits carry a scale, s_mj = inv_temp H_m . T_j, and a call may
+// leave key j = m out of row m's softmax (exclude_diagonal, M = N).  A row can then meet a tile or a chunk whose only key
+// is its own: such a tile has no finite logit, contributes nothing and leaves the running max at -inf, and the finish
+// gives a chunk whose max is -inf the weight 0.  Pass 2 can add the finished dL/dH row r into the dL/dT row r it owns
+// (add_gh_into_gt, M = N): a caller that passes one matrix as H and T gets its whole gradient without another launch.
 #include <algorithm>
 #include <cmath>
 
@@ -333,6 +340,10 @@ struct CeArgs {
   const int32_t* label;  // M
   int64_t M, N;
   float scale;
+  // the pair cross-entropy only (PAIR): s = inv_temp H.T, gradients times gscale = scale inv_temp
+  float inv_temp, gscale;
+  int32_t exclude;   // key j = m is left out of row m's softmax (M == N)
+  int32_t add_gh;    // pass 2 stores gt_r + gh_r (M == N)
   double* loss;
   float* gh;
   float* gt;
@@ -371,7 +382,8 @@ __device__ __forceinline__ float ce_row_max4(float v) {
 
 // pass 1: R = the rows of H, C = a key chunk of T, W = exp(s - running max)  -> per chunk (max, sum W, sum W T_j)
 // pass 2: R = the rows of T, C = all rows of H,    W = exp(s - lse_c) - [label_c == r]  -> dL/dT_r / scale
-template <int D, bool PASS2>
+// PAIR: s is inv_temp times the product; with P.exclude the pair (row m, key m) has s = -inf in pass 1 and W = 0 in pass 2
+template <int D, bool PASS2, bool PAIR>
 __global__ __launch_bounds__(256) void ce_pass(CeArgs P) {
   __shared__ float cs[kCtCTile * kRtStride<D>];
   __shared__ float clse[kCtCTile];
@@ -390,6 +402,7 @@ __global__ __launch_bounds__(256) void ce_pass(CeArgs P) {
   const int g = L.g, j16 = L.j16;
   const int64_t r = rtile * kCtRows + L.wave * 16 + j16;
   const bool rok = r < nR;
+  const bool excl = PAIR && P.exclude != 0;
 
   float rf[D / 4];
 #pragma unroll
@@ -415,27 +428,36 @@ __global__ __launch_bounds__(256) void ce_pass(CeArgs P) {
     f32x4 s[kCtCTile / 16];
 #pragma unroll
     for (int sub = 0; sub < kCtCTile / 16; ++sub) s[sub] = score16<D>(cs, sub, j16, g, rf);
+    if (PAIR) {
+#pragma unroll
+      for (int sub = 0; sub < kCtCTile / 16; ++sub) s[sub] *= P.inv_temp;
+    }
     if (!PASS2) {
       // the keys past the chunk's end are -inf before the max; a tile holds at least one key, so the max is finite
+      // (PAIR with exclusion: the row's own key is -inf too, and a tile may hold no other -- see m_sub below)
       float mx = -INFINITY;
 #pragma unroll
       for (int sub = 0; sub < kCtCTile / 16; ++sub)
 #pragma unroll
         for (int reg = 0; reg < 4; ++reg) {
-          if (c0 + sub * 16 + 4 * g + reg >= cend) s[sub][reg] = -INFINITY;
+          const int64_t c = c0 + sub * 16 + 4 * g + reg;
+          if (c >= cend || (excl && c == r)) s[sub][reg] = -INFINITY;
           mx = fmaxf(mx, s[sub][reg]);
         }
       const float m_new = fmaxf(m, ce_row_max4(mx));
-      const float alpha = expf(m - m_new);  // 0 on the first tile (m = -inf), 1 while the max stands
+      // 0 on the first tile (m = -inf), 1 while the max stands.  PAIR: while the row has met no key, m and m_new are both
+      // -inf and m - m_new is NaN: nothing is held yet, so the factor is 0, and the tile's weights exp(-inf - 0) are 0
+      const float alpha = PAIR && m == -INFINITY ? 0.f : expf(m - m_new);
       rs *= (double)alpha;
 #pragma unroll
       for (int b = 0; b < D / 16; ++b) o[b] *= alpha;
       m = m_new;
+      const float m_sub = PAIR && m == -INFINITY ? 0.f : m;
 #pragma unroll
       for (int sub = 0; sub < kCtCTile / 16; ++sub)
 #pragma unroll
         for (int reg = 0; reg < 4; ++reg) {
-          const float w = expf(s[sub][reg] - m);
+          const float w = expf(s[sub][reg] - m_sub);
           rs += (double)w;
           s[sub][reg] = w;
         }
@@ -447,6 +469,8 @@ __global__ __launch_bounds__(256) void ce_pass(CeArgs P) {
           const int ci = sub * 16 + 4 * g + reg;
           float w = expf(s[sub][reg] - clse[ci]);
           if ((int64_t)clab[ci] == r) w -= 1.f;
+          // (after the one-hot: a row that names its own excluded key has none, here as in the finish)
+          if (excl && c0 + ci == r) w = 0.f;
           s[sub][reg] = w;
         }
     }
@@ -473,15 +497,23 @@ __global__ __launch_bounds__(256) void ce_pass(CeArgs P) {
     store_acc<D>(o, P.part_o, row, g);
   } else {
     if (!rok) return;
-    const float k = P.scale;
+    const float k = PAIR ? P.gscale : P.scale;
 #pragma unroll
     for (int b = 0; b < D / 16; ++b) o[b] *= k;
+    if (PAIR && P.add_gh) {
+      // (M == N: row r of dL/dH exists, and the finish that wrote it ran before this launch on the same stream)
+#pragma unroll
+      for (int b = 0; b < D / 16; ++b) {
+        const float4 h = reinterpret_cast<const float4*>(P.gh + r * D + 16 * b + 4 * g)[0];
+        o[b] += f32x4{h.x, h.y, h.z, h.w};
+      }
+    }
     store_acc<D>(o, P.gt, r, g);
   }
 }
 
 // per row: the chunk partials merged in chunk order under the row's largest max -> lse, loss term, dL/dH
-template <int D>
+template <int D, bool PAIR>
 __global__ __launch_bounds__(256) void ce_finish(CeArgs P) {
   constexpr int LPR = D / 4, RPB = 256 / LPR;
   const int64_t b = (int64_t)blockIdx.x * RPB + threadIdx.x / LPR;
@@ -492,23 +524,26 @@ __global__ __launch_bounds__(256) void ce_finish(CeArgs P) {
   double rs = 0.0;
   float4 o = srh::f4_zero();
   for (int64_t c = 0; c < P.chunks; ++c) {
-    const float a = expf(P.part_m[c * P.M + b] - mm);
+    const float pm = P.part_m[c * P.M + b];
+    const float a = PAIR && pm == -INFINITY ? 0.f : expf(pm - mm);  // (PAIR: a chunk that held only the row's own key)
     rs += P.part_rs[c * P.M + b] * (double)a;
     o = srh::f4_fma(a, reinterpret_cast<const float4*>(P.part_o + (c * P.M + b) * D)[lane], o);
   }
   const int64_t j = P.label[b];
-  const bool jok = j >= 0 && j < P.N;  // (a label outside the table reads nothing and makes the loss NaN)
+  // (a label outside the table reads nothing and makes the loss NaN; so does the row's own key when it is excluded)
+  const bool jok = j >= 0 && j < P.N && !(PAIR && P.exclude && j == b);
   const float4 h = reinterpret_cast<const float4*>(P.h + b * D)[lane];
   const float4 t = jok ? reinterpret_cast<const float4*>(P.t + j * D)[lane] : srh::f4_zero();
   double spos = (double)h.x * (double)t.x + (double)h.y * (double)t.y + (double)h.z * (double)t.z + (double)h.w * (double)t.w;
 #pragma unroll
   for (int w = 1; w < LPR; w <<= 1) spos += __shfl_xor(spos, w);
+  if (PAIR) spos *= (double)P.inv_temp;
   const double lse = (double)mm + log(rs);
   if (lane == 0) {
     P.row_loss[b] = jok ? lse - spos : (double)NAN;
     P.lse[b] = (float)lse;
   }
-  const float inv_rs = (float)(1.0 / rs), k = P.scale;
+  const float inv_rs = (float)(1.0 / rs), k = PAIR ? P.gscale : P.scale;
   reinterpret_cast<float4*>(P.gh + b * D)[lane] = make_float4(k * (o.x * inv_rs - t.x), k * (o.y * inv_rs - t.y),
                                                                k * (o.z * inv_rs - t.z), k * (o.w * inv_rs - t.w));
 }
@@ -519,15 +554,15 @@ __global__ __launch_bounds__(256) void ce_loss(CeArgs P) {
   if (threadIdx.x == 0) P.loss[0] = (double)P.scale * s;
 }
 
-template <int D>
+template <int D, bool PAIR>
 srh_status_t launch_ce(const CeArgs& a, hipStream_t st) {
   constexpr int RPB = 256 / (D / 4);
   const int64_t p1 = (a.M + kCtRows - 1) / kCtRows * a.chunks, p2 = (a.N + kCtRows - 1) / kCtRows;
-  ce_pass<D, false><<<(unsigned)p1, 256, 0, st>>>(a);
+  ce_pass<D, false, PAIR><<<(unsigned)p1, 256, 0, st>>>(a);
   SRH_LAUNCH_CHECK();
-  ce_finish<D><<<(unsigned)((a.M + RPB - 1) / RPB), 256, 0, st>>>(a);
+  ce_finish<D, PAIR><<<(unsigned)((a.M + RPB - 1) / RPB), 256, 0, st>>>(a);
   SRH_LAUNCH_CHECK();
-  ce_pass<D, true><<<(unsigned)p2, 256, 0, st>>>(a);
+  ce_pass<D, true, PAIR><<<(unsigned)p2, 256, 0, st>>>(a);
   SRH_LAUNCH_CHECK();
   ce_loss<<<1, 256, 0, st>>>(a);
   SRH_LAUNCH_CHECK();
@@ -607,7 +642,37 @@ srh_status_t srh_table_ce_fwd_bwd(const float* d_h, int64_t M, const float* d_t,
   a.loss = d_loss; a.gh = d_gh; a.gt = d_gt;
   ce_layout(a, d_ws, d);
   hipStream_t st = srh::as_stream(stream);
-  return d == 64 ? launch_ce<64>(a, st) : launch_ce<128>(a, st);
+  return d == 64 ? launch_ce<64, false>(a, st) : launch_ce<128, false>(a, st);
+}
+
+int64_t srh_pair_ce_ws_bytes(int64_t M, int64_t N, int32_t d) {
+  if (M <= 0 || N <= 0 || (d != 64 && d != 128)) return 0;
+  return ce_ws_bytes(M, N, d);
+}
+
+srh_status_t srh_pair_ce_fwd_bwd(const float* d_h, int64_t M, const float* d_t, int64_t N, int32_t d,
+                                 const int32_t* d_labels, float inv_temp, float loss_scale, int32_t exclude_diagonal,
+                                 int32_t add_gh_into_gt, double* d_loss, float* d_gh, float* d_gt, void* d_ws,
+                                 void* stream) {
+  SRH_REQUIRE(M > 0 && M < (int64_t(1) << 31) && N > 0 && N < (int64_t(1) << 31), "pair_ce_fwd_bwd: bad M / N");
+  SRH_SUPPORTED(d == 64 || d == 128, "pair_ce_fwd_bwd: d=%d unsupported (64 or 128; narrower rows are zero-padded)", d);
+  SRH_REQUIRE(d_h && d_t && d_labels && d_loss && d_gh && d_gt && d_ws, "pair_ce_fwd_bwd: null argument");
+  SRH_REQUIRE(std::isfinite(loss_scale), "pair_ce_fwd_bwd: the loss scale must be finite");
+  SRH_REQUIRE(std::isfinite(inv_temp) && inv_temp > 0.f, "pair_ce_fwd_bwd: inv_temp must be positive and finite");
+  SRH_REQUIRE(!exclude_diagonal || M == N, "pair_ce_fwd_bwd: exclude_diagonal needs M == N (got %lld x %lld)",
+              (long long)M, (long long)N);
+  SRH_REQUIRE(!exclude_diagonal || N > 1, "pair_ce_fwd_bwd: exclude_diagonal with N = 1 leaves no key in any row");
+  SRH_REQUIRE(!add_gh_into_gt || M == N, "pair_ce_fwd_bwd: add_gh_into_gt needs M == N (got %lld x %lld)", (long long)M,
+              (long long)N);
+  SRH_REQUIRE(d_gh != d_gt, "pair_ce_fwd_bwd: d_gh and d_gt must be two buffers");
+  CeArgs a{};
+  a.h = d_h; a.t = d_t; a.label = d_labels; a.M = M; a.N = N; a.scale = loss_scale;
+  a.inv_temp = inv_temp; a.gscale = loss_scale * inv_temp;
+  a.exclude = exclude_diagonal ? 1 : 0; a.add_gh = add_gh_into_gt ? 1 : 0;
+  a.loss = d_loss; a.gh = d_gh; a.gt = d_gt;
+  ce_layout(a, d_ws, d);
+  hipStream_t st = srh::as_stream(stream);
+  return d == 64 ? launch_ce<64, true>(a, st) : launch_ce<128, true>(a, st);
 }
 
 }  // extern "C"

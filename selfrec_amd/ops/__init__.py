@@ -12,6 +12,8 @@ from .contrastive import (KMEANS_MAX_POINTS_PER_CENTROID, KMEANS_SPLIT_EPS, Batc
                           table_nce_fwd_bwd, table_nce_ws)
 from .host import Sampler, find_k_largest_host, find_k_largest_host_f64, unique_first
 from .knn import KNN_MAX_K, knn_neighbours, knn_score_topk, knn_score_ws
+from .losses import (TRIPLET_MARGIN, KlDivFn, PairCeFn, SelfPairCeFn, TripletFn, kl_div_fwd_bwd, pair_ce_fwd_bwd,
+                     triplet_fwd_bwd)
 from .mhcn import GATE_MAX, ChanMixFn, GateFn, MimFn, chan_mix_bwd, chan_mix_fwd, gate_bwd, gate_fwd, mim_fwd_bwd
 from .mixgcf import MIXUP_MAX_HOPS, MixupFn, mixup_bwd, mixup_fwd, mixup_supported
 from .ranking import (gemm_nt, metric_rows, score_mask_topk, score_mask_topk_filtered, topk_hit_flags, topk_rows,
@@ -45,5 +47,6 @@ __all__ = """
     GatherRowsFn seq_embed_supported seq_embed_fwd live_plan_host live_plan rows_live_sum SeqEmbedFn SeqBceLiveFn
     rows_l2norm_fwd rows_l2norm_bwd NormPropFn RowsL2NormFn tri_nd_fwd_bwd TriNdFn gate_fwd gate_bwd GateFn
     chan_mix_fwd chan_mix_bwd ChanMixFn mim_fwd_bwd MimFn mixup_supported mixup_fwd mixup_bwd MixupFn au_supported au_fwd_bwd
-    AlignUniformFn boot_supported boot_fwd_bwd BootstrapLossFn rows_momentum
+    AlignUniformFn boot_supported boot_fwd_bwd BootstrapLossFn rows_momentum pair_ce_fwd_bwd PairCeFn SelfPairCeFn
+    triplet_fwd_bwd TripletFn kl_div_fwd_bwd KlDivFn
 """.split()

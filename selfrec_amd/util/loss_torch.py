@@ -1,6 +1,6 @@
-"""Differentiable losses with the signatures of reference util/loss_torch.py
-(``bpr_loss`` :6-10, ``l2_reg_loss`` :18-22, ``batch_softmax_loss`` :25-32, ``InfoNCE`` :35-50), computed by fused HIP
-forward+backward kernels.
+"""Differentiable losses with the signatures of reference util/loss_torch.py -- all seven of its public functions
+(``bpr_loss`` :6-10, ``triplet_loss`` :12-16, ``l2_reg_loss`` :18-22, ``batch_softmax_loss`` :25-32, ``InfoNCE`` :35-50,
+``info_nce`` :54-88, ``kl_divergence`` :91-94), computed by fused HIP forward+backward kernels.
 
 What runs where:
   * 2-D fp32 HIP tensors -- what every model file of the reference passes once ``.cuda()`` has run -- ALWAYS take the
@@ -9,11 +9,19 @@ What runs where:
     columns change no inner product, norm or F.normalize result and receive exactly zero gradient -- BPR up to
     256 columns, InfoNCE up to 256 (above 128: the split path only), the regulariser any size.  bpr_loss's three operands
     broadcast against each other as the reference's torch.mul does (_bpr_operands); no rows: the torch expression (nan).
+    triplet_loss follows bpr_loss in all of this; kl_divergence takes any R x C; info_nce, InfoNCE(b_cos=False) and
+    InfoNCE below temperature 0.03 take the pair cross-entropy (ops.pair_ce_fwd_bwd), rows up to 128 columns.
   * CPU tensors, other dtypes, other ranks: the reference's own torch expression (the arithmetic of loss_torch.py:6-50
     restated below), so code that calls these functions off the device -- unit tests of a model file, a CPU dry run --
     behaves as it does with the reference.  This is not a fallback for the HIP path: device fp32 input never reaches it.
-  * InfoNCE or BPR on HIP rows wider than 256 columns: the same torch expression on the device (rocBLAS +
-    ATen), announced once with a RuntimeWarning -- no kernel of this package serves those widths yet.
+  * InfoNCE, BPR or triplet_loss on HIP rows wider than 256 columns, and the pair cross-entropy routes above 128: the
+    same torch expression on the device (rocBLAS + ATen), announced once with a RuntimeWarning -- no kernel of this
+    package serves those widths yet.
+  * The cosine forms that go through the pair cross-entropy (info_nce(sim='cos'), InfoNCE(b_cos=True) below temperature
+    0.03) normalise their rows with ops.RowsL2NormFn, x / max(|x|, 1e-6).  F.normalize clamps at 1e-12 and
+    cosine_similarity at 1e-8: rows with 0 < |x| < 1e-6 deviate (value and gradient), and an exactly zero row has the
+    reference's forward value (all its similarities are 0) but a gradient of g * 1e6 where the reference has g * 1e8
+    (cosine_similarity) or g * 1e12 (F.normalize).  No device-to-host check looks for such rows.
 """
 import warnings
 
@@ -127,6 +135,28 @@ class _L2RegFn(torch.autograd.Function):
         return (None, *gxs)
 
 
+def _triplet_expression(user_emb, pos_item_emb, neg_item_emb):
+    """loss_torch.py:12-16"""
+    pos_score = ((user_emb - pos_item_emb) ** 2).sum(dim=1)
+    neg_score = ((user_emb - neg_item_emb) ** 2).sum(dim=1)
+    loss = F.relu(pos_score - neg_score + 0.5)
+    return torch.mean(loss)
+
+
+def triplet_loss(user_emb, pos_item_emb, neg_item_emb):
+    """mean_b relu(|u_b - p_b|^2 - |u_b - n_b|^2 + 0.5): one HIP call (ops.TripletFn) produces the loss and the three
+    gradients.  The operands broadcast as bpr_loss's; rows up to 256 columns."""
+    if _on_hip_path(user_emb, pos_item_emb, neg_item_emb):
+        u, p, n = _bpr_operands(user_emb, pos_item_emb, neg_item_emb)
+        rows, d = int(u.shape[0]), int(u.shape[1])
+        if rows > 0 and 0 < d <= ops.ROW_WIDTHS[-1]:
+            return ops.TripletFn.apply(u, p, n)
+        if d > ops.ROW_WIDTHS[-1]:
+            _announce_wide("triplet_loss", d, ops.ROW_WIDTHS[-1])
+        # (no rows: the mean of nothing, nan, as the reference returns -- the expression below)
+    return _triplet_expression(user_emb, pos_item_emb, neg_item_emb)
+
+
 def l2_reg_loss(reg, *args):
     if args and len(args) <= _L2RegFn.MAX_BLOCKS and all(_on_hip_path(e) and e.numel() > 0 for e in args):
         return _L2RegFn.apply(float(reg), *args)
@@ -195,14 +225,93 @@ def _infonce_expression(view1, view2, temperature, b_cos=True):
     return -score.mean()
 
 
+INFONCE_UNIT_MIN_TAU = 0.03      # below it the unit-row kernels' exp((s - 1) / tau) underflows (csrc/losses.hip): pair CE
+
+
+def _arange_labels(n, device, shift=0):
+    labels = torch.arange(n, dtype=torch.int32, device=device)
+    return labels if not shift else (labels + shift) % n
+
+
 def InfoNCE(view1, view2, temperature: float, b_cos: bool = True):
+    """b_cos=True at temperature >= 0.03: the unit-row InfoNCE kernels (srh_infonce_fwd_bwd), as before.  b_cos=False, and
+    b_cos=True below 0.03 (rows normalised by ops.RowsL2NormFn first: F.normalize on every row of norm >= 1e-6, see the
+    module docstring): the max-subtracted pair cross-entropy ops.PairCeFn with identity labels, 1 / temperature and
+    1 / n, rows up to 128 columns.  ops.set_infonce_precision's process default (the split-16 products) has no meaning on
+    that route: its products are f32 MFMA."""
     if not _on_hip_path(view1, view2):
         return _infonce_expression(view1, view2, temperature, b_cos)
-    if not b_cos:
-        raise ops.SelfrecHipError("InfoNCE(b_cos=False) has no caller in the reference and no HIP kernel")
     if view1.shape != view2.shape:
         raise ops.SelfrecHipError("InfoNCE: the two views must have the same shape")
-    if int(view1.shape[1]) > ops.NCE_WIDTHS[-1]:
-        _announce_wide("InfoNCE", int(view1.shape[1]), ops.NCE_WIDTHS[-1])
-        return _infonce_expression(view1, view2, temperature, True)
-    return _InfoNceFn.apply(view1, view2, float(temperature))
+    d = int(view1.shape[1])
+    if b_cos and float(temperature) >= INFONCE_UNIT_MIN_TAU:
+        if d > ops.NCE_WIDTHS[-1]:
+            _announce_wide("InfoNCE", d, ops.NCE_WIDTHS[-1])
+            return _infonce_expression(view1, view2, temperature, True)
+        return _InfoNceFn.apply(view1, view2, float(temperature))
+    n = int(view1.shape[0])
+    if d > ops.TABLE_NCE_WIDTHS[-1] or n == 0 or d == 0:
+        if d > ops.TABLE_NCE_WIDTHS[-1]:
+            _announce_wide("InfoNCE (b_cos=False, or temperature < 0.03)", d, ops.TABLE_NCE_WIDTHS[-1])
+        return _infonce_expression(view1, view2, temperature, b_cos)
+    if b_cos:
+        view1, view2 = ops.RowsL2NormFn.apply(view1), ops.RowsL2NormFn.apply(view2)
+    return ops.PairCeFn.apply(view1, view2, _arange_labels(n, view1.device), 1.0 / float(temperature), 1.0 / n)
+
+
+def _info_nce_expression(z_i, z_j, temp, batch_size, sim='dot'):
+    """loss_torch.py:54-88"""
+    N = 2 * batch_size
+    z = torch.cat((z_i, z_j), dim=0)
+    if sim == 'cos':
+        sim = F.cosine_similarity(z.unsqueeze(1), z.unsqueeze(0), dim=2) / temp
+    elif sim == 'dot':
+        sim = torch.mm(z, z.T) / temp
+    sim_i_j = torch.diag(sim, batch_size)
+    sim_j_i = torch.diag(sim, -batch_size)
+    positive_samples = torch.cat((sim_i_j, sim_j_i), dim=0).reshape(N, 1)
+    mask = torch.ones((N, N), dtype=bool)
+    mask = mask.fill_diagonal_(0)
+    for i in range(batch_size):
+        mask[i, batch_size + i] = 0
+        mask[batch_size + i, i] = 0
+    negative_samples = sim[mask].reshape(N, -1)
+    labels = torch.zeros(N).to(positive_samples.device).long()
+    logits = torch.cat((positive_samples, negative_samples), dim=1)
+    return F.cross_entropy(logits, labels)
+
+
+def info_nce(z_i, z_j, temp, batch_size, sim='dot'):
+    """RecBole's NT-Xent: z = cat(z_i, z_j) (2B rows), every row against all others, its positive the same item's other
+    view.  One pair cross-entropy of z against itself without the diagonal (ops.SelfPairCeFn: labels (m + B) mod 2B,
+    1 / temp, 1 / 2B); no (2B)^2 array is made.  sim='cos' normalises the rows first (ops.RowsL2NormFn, clamp 1e-6 where
+    cosine_similarity clamps at 1e-8: module docstring).  batch_size != z_i.shape[0], unequal shapes or no rows: the
+    reference's expression, which raises what the reference raises.  Rows up to 128 columns."""
+    if sim not in ('dot', 'cos'):
+        raise ValueError(f"info_nce: sim must be 'dot' or 'cos', got {sim!r}")
+    if not _on_hip_path(z_i, z_j) or z_i.shape != z_j.shape or int(z_i.shape[0]) != batch_size or batch_size < 1 \
+            or int(z_i.shape[1]) == 0:
+        return _info_nce_expression(z_i, z_j, temp, batch_size, sim)
+    B, d = int(z_i.shape[0]), int(z_i.shape[1])
+    if d > ops.TABLE_NCE_WIDTHS[-1]:
+        _announce_wide("info_nce", d, ops.TABLE_NCE_WIDTHS[-1])
+        return _info_nce_expression(z_i, z_j, temp, batch_size, sim)
+    z = torch.cat((z_i, z_j), dim=0)
+    if sim == 'cos':
+        z = ops.RowsL2NormFn.apply(z)
+    return ops.SelfPairCeFn.apply(z, _arange_labels(2 * B, z.device, B), 1.0 / float(temp), 1.0 / (2 * B))
+
+
+def _kl_expression(p_logit, q_logit):
+    """loss_torch.py:91-94"""
+    p = F.softmax(p_logit, dim=-1)
+    kl = torch.sum(p * (F.log_softmax(p_logit, dim=-1) - F.log_softmax(q_logit, dim=-1)), 1)
+    return torch.mean(kl)
+
+
+def kl_divergence(p_logit, q_logit):
+    """mean_r KL(softmax(p_logit_r) || softmax(q_logit_r)) of (R x C) logits: one HIP call (ops.KlDivFn) produces the loss
+    and both gradients, any R >= 1 and C >= 1."""
+    if _on_hip_path(p_logit, q_logit) and p_logit.shape == q_logit.shape and p_logit.numel() > 0:
+        return ops.KlDivFn.apply(p_logit, q_logit)
+    return _kl_expression(p_logit, q_logit)
