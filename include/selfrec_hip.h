@@ -982,6 +982,30 @@ srh_status_t srh_table_ce_fwd_bwd(const float* d_h, int64_t M, const float* d_t,
                                   void* d_ws, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * (a-25) The attention core of (a-16) and (a-17) for sequences of up to 512 positions (max.len above 64).
+ *
+ * srh_seq_attn_tiled_fwd_f32 / srh_seq_attn_tiled_bwd_f32: the layouts, formulas, d_lse and dropout contract (keep mask
+ *   given, or drawn at counter rng_counter + (b H + h) L + row, float4 col / 4, word col % 4, keep = u01(word) >= drop_p;
+ *   B H L counters per call) of srh_seq_attn_fwd_f32 / _bwd_f32 when causal != 0 and of srh_seq_attn_full_fwd_f32 /
+ *   _bwd_f32 when causal == 0.  The forward walks 64-key blocks with a running row maximum and sum; only d_out and d_lse
+ *   are written.  The backward takes the forward's d_out next to its d_lse (rowsum(m dP P) = dO_i . out_i, dropout
+ *   included) and runs two launches: dQ by query block over the key blocks, dK and dV by key block over the query
+ *   blocks, both in ascending order.  A query row that sees a single key (row 0 when causal, L = 1 otherwise) has
+ *   dS = 0 identically and contributes exact zeros; a query row whose keep mask is empty gives exact zeros in d_out and
+ *   d_gq, a key nobody keeps exact zeros in d_gv.
+ *   Envelope: 1 <= L <= 512, dh 32 or 64, H dh <= 128, any B >= 1; outside it SRH_ERR_UNSUPPORTED with a message, a
+ *   null argument or drop_p outside [0, 1) SRH_ERR_INVALID_ARG, all before any launch.  No float atomics and no
+ *   scratch: one producer and one summation order per output element, the same bits on every call.
+ * ---------------------------------------------------------------------------------- */
+srh_status_t srh_seq_attn_tiled_fwd_f32(const float* d_q, const float* d_k, const float* d_v, int64_t B, int32_t L,
+                                        int32_t H, int32_t dh, int32_t causal, const uint8_t* d_keep, uint64_t rng_seed,
+                                        uint64_t rng_counter, float drop_p, float* d_out, float* d_lse, void* stream);
+srh_status_t srh_seq_attn_tiled_bwd_f32(const float* d_q, const float* d_k, const float* d_v, const float* d_out,
+                                        const float* d_go, const float* d_lse, int64_t B, int32_t L, int32_t H, int32_t dh,
+                                        int32_t causal, const uint8_t* d_keep, uint64_t rng_seed, uint64_t rng_counter,
+                                        float drop_p, float* d_gq, float* d_gk, float* d_gv, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * (a-18) CL4SRec -- the embedding front of SASRec_Model.forward (model/sequential/SASRec.py:70-76: both gathers, the
  * scale, the sum, nn.Dropout, the padding mask) as model/sequential/CL4SRec.py:36-55 calls it three times a step, and the
  * table gradients behind it and behind calculate_loss.

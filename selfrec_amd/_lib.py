@@ -229,6 +229,10 @@ SIGNATURES = {
     "srh_seq_attn_full_fwd_f32": (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _u64, _u64, _f32, _vp, _vp, _vp]),
     "srh_seq_attn_full_bwd_f32": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _u64, _u64, _f32, _vp, _vp,
                                          _vp, _vp]),
+    "srh_seq_attn_tiled_fwd_f32": (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _u64, _u64, _f32, _vp, _vp,
+                                          _vp]),
+    "srh_seq_attn_tiled_bwd_f32": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _u64, _u64, _f32,
+                                          _vp, _vp, _vp, _vp]),
     "srh_table_ce_ws_bytes": (_i64, [_i64, _i64, _i32]),
     "srh_table_ce_fwd_bwd": (_i32, [_vp, _i64, _vp, _i64, _i32, _vp, _f32, _vp, _vp, _vp, _vp, _vp]),
     "srh_pair_ce_ws_bytes": (_i64, [_i64, _i64, _i32]),

@@ -373,11 +373,19 @@ __device__ __forceinline__ uint32_t lowbias32(uint32_t x) {
   x ^= x >> 16; x *= 0x7feb352dU; x ^= x >> 15; x *= 0x846ca68bU; x ^= x >> 16;
   return x;
 }
-__device__ __forceinline__ uint4 counter_rng4(uint64_t ctr, uint32_t sub, uint32_t seed_lo, uint32_t seed_hi) {
+__device__ __forceinline__ uint32_t counter_rng_base(uint64_t ctr, uint32_t sub, uint32_t seed_lo, uint32_t seed_hi) {
   const uint32_t key = lowbias32((uint32_t)ctr ^ seed_lo) + lowbias32((uint32_t)(ctr >> 32) ^ seed_hi);
-  const uint32_t base = key + sub * 0x9E3779B1U;
-  return make_uint4(lowbias32(base), lowbias32(base + 0x85EBCA6BU), lowbias32(base + 0xC2B2AE35U),
-                    lowbias32(base + 0x27D4EB2FU));
+  return key + sub * 0x9E3779B1U;
+}
+constexpr uint32_t kRngWord1 = 0x85EBCA6BU, kRngWord2 = 0xC2B2AE35U, kRngWord3 = 0x27D4EB2FU;
+__device__ __forceinline__ uint4 counter_rng4(uint64_t ctr, uint32_t sub, uint32_t seed_lo, uint32_t seed_hi) {
+  const uint32_t base = counter_rng_base(ctr, sub, seed_lo, seed_hi);
+  return make_uint4(lowbias32(base), lowbias32(base + kRngWord1), lowbias32(base + kRngWord2), lowbias32(base + kRngWord3));
+}
+// word w (0..3: x, y, z, w) of counter_rng4 alone, for a consumer that owns one element of the float4
+__device__ __forceinline__ uint32_t counter_rng_word(uint64_t ctr, uint32_t sub, int w, uint32_t seed_lo, uint32_t seed_hi) {
+  const uint32_t base = counter_rng_base(ctr, sub, seed_lo, seed_hi);
+  return lowbias32(base + (w == 0 ? 0U : w == 1 ? kRngWord1 : w == 2 ? kRngWord2 : kRngWord3));
 }
 __device__ __forceinline__ float u01(uint32_t x) { return (float)(x >> 8) * (1.0f / 16777216.0f); }
 

@@ -22,6 +22,14 @@
 // masked before the row max (for a causal row they lie above the diagonal and need no test of their own), the dropout
 // multiplier is drawn for the whole row, and pass 2 sums over all the query tiles from 0, where rows >= L hold zeros.
 //
+// Longer sequences (64 < L <= 512) take the tiled kernels (srh_seq_attn_tiled_*): the same wave, score and
+// seam code over 64 x 64 blocks.  attn_tiled_fwd owns one 64-row query block of a (sequence, head), walks the key blocks in
+// ascending order with K and V of one block in LDS, and rescales a per-row running maximum, sum and output at each block.
+// attn_tiled_bwd_q has the same ownership and sums dQ over the key blocks; attn_tiled_bwd_kv turns it round: a workgroup
+// owns a key block, its waves hold their keys' K and V rows as the register operand, the scaled Q and dO of one query block
+// sit in LDS, S^T and dP~^T come out of the same scores() with the roles swapped, and dV and dK are summed over the query
+// blocks in ascending order.  Both recompute P from lse and take delta = dO . O from the forward's output.
+//
 // Dropout on P: keep[b][h][row][col] injected as bytes, or drawn from the counter RNG of common.h at counter
 // rng_counter + (b H + h) L + row, float4 number col / 4, word col % 4 (keep = u01(word) >= p); the backward redraws it.
 //
@@ -51,6 +59,7 @@ enum { DROP_NONE = 0, DROP_GIVEN = 1, DROP_DRAWN = 2 };
 struct AttnArgs {
   const float *q, *k, *v;
   const float *go, *lse_in;       // backward only
+  const float* out_in;            // tiled backward only: the forward's out
   float *out, *lse;               // forward only
   float *gq, *gk, *gv;            // backward only
   const uint8_t* keep;
@@ -61,13 +70,15 @@ struct AttnArgs {
   float drop_p, drop_scale, qscale;
 };
 
-// rows [0, L) of one head's (L x DH) slice (row stride E floats) -> dst[r][c] with row stride DH + 4; rows >= L zero
-template <int DH>
-__device__ __forceinline__ void stage_tile(float* dst, const float* src, const int L, const int E) {
+// rows [0, L) of one head's (L x DH) slice (row stride E floats) -> dst[r][c] with row stride DH + 4; rows >= L zero.
+// SCALED: every element times scale, rounded once (the tiled backward's Q block: the bits of the forward's query operand)
+template <int DH, bool SCALED = false>
+__device__ __forceinline__ void stage_tile(float* dst, const float* src, const int L, const int E, const float scale = 1.f) {
   constexpr int LD = DH + 4;
   for (int e = threadIdx.x; e < kMaxL * (DH / 4); e += 256) {
     const int r = e / (DH / 4), v = e % (DH / 4);
-    const float4 x = r < L ? *reinterpret_cast<const float4*>(src + (int64_t)r * E + 4 * v) : f4_zero();
+    float4 x = r < L ? *reinterpret_cast<const float4*>(src + (int64_t)r * E + 4 * v) : f4_zero();
+    if constexpr (SCALED) x = make_float4(x.x * scale, x.y * scale, x.z * scale, x.w * scale);
     *reinterpret_cast<float4*>(&dst[r * LD + 4 * v]) = x;
   }
 }
@@ -89,6 +100,14 @@ __device__ __forceinline__ void drop_mult4(const AttnArgs& a, const int64_t bh, 
     m[2] = u01(w.z) >= a.drop_p ? a.drop_scale : 0.f;
     m[3] = u01(w.w) >= a.drop_p ? a.drop_scale : 0.f;
   }
+}
+
+// the dropout multiplier of the single element P[row][col] (row, col < L): drop_mult4's value for it
+__device__ __forceinline__ float drop_mult1(const AttnArgs& a, const int64_t bh, const int row, const int col) {
+  if (a.drop == DROP_NONE) return 1.f;
+  if (a.drop == DROP_GIVEN) return a.keep[(bh * a.L + row) * a.L + col] != 0 ? a.drop_scale : 0.f;
+  const uint32_t w = counter_rng_word(a.ctr + (uint64_t)(bh * a.L + row), (uint32_t)(col >> 2), col & 3, a.seed_lo, a.seed_hi);
+  return u01(w) >= a.drop_p ? a.drop_scale : 0.f;
 }
 
 // sum / max over the four lanes (g = 0..3) that share query row j16: the same bits in all four
@@ -342,11 +361,281 @@ __global__ __launch_bounds__(256) void attn_bwd(AttnArgs a) {
   }
 }
 
+// ---- tiled: 64 < L <= 512 -----------------------------------------------------------------------------
+constexpr int kTiledMaxL = 512;
+
+// what a tiled workgroup is: block blk of the nB 64-row blocks of (sequence, head) bh
+struct TiledOwner {
+  int64_t bh, base;       // base: the float offset of row 0 of the head's slice
+  int blk, nB, E;
+};
+template <int DH>
+__device__ __forceinline__ TiledOwner tiled_owner(const AttnArgs& a) {
+  TiledOwner o;
+  o.nB = (a.L + kMaxL - 1) / kMaxL;
+  o.bh = blockIdx.x / o.nB;
+  o.blk = (int)(blockIdx.x % o.nB);
+  o.E = a.H * DH;
+  o.base = (o.bh / a.H) * a.L * o.E + (o.bh % a.H) * DH;
+  return o;
+}
+
+// the lane's share of dO_row . O_row: the columns 4k + g, k ascending.  The row's delta is the sum of the four shares in
+// the order (g0 + g1) + (g2 + g3) -- row_sum4 in the dQ kernel, two steps over neighbouring lanes in the dK / dV kernel.
+template <int DH>
+__device__ __forceinline__ float delta_share(const float* go_row, const float* out_row, const int g) {
+  float s = 0.f;
+#pragma unroll
+  for (int k = 0; k < DH / 4; ++k) s += go_row[4 * k + g] * out_row[4 * k + g];
+  return s;
+}
+
+// a query row that sees one key only (row 0 of a causal call, the row of L = 1) has P = 1 and dS = 0 identically; delta
+// from dO . O and dP~ from the MFMA round differently, so the identity is written, not their difference
+template <bool CAUSAL>
+__device__ __forceinline__ bool lone_key(const int row, const int L) {
+  return CAUSAL ? row == 0 : L == 1;
+}
+
+// one key block of the forward: DIAG = the causal block on the diagonal (local indices against the wave's own tile), else
+// every key below Lk is seen
+template <int DH, bool DIAG>
+__device__ __forceinline__ void tiled_fwd_block(const AttnArgs& a, const float* Ks, const float* Vs,
+                                                const float (&qf)[DH / 4], const int64_t bh, const int row, const bool rok,
+                                                const int kb, const int Lk, const int wave, const int g, const int j16,
+                                                float& mrun, float& lrun, f32x4 (&ot)[DH / 16]) {
+  const int rloc = 16 * wave + j16;
+  f32x4 st[4];
+  scores<DH, DIAG>(Ks, qf, wave, Lk, g, j16, st);
+  float mx = -INFINITY;
+#pragma unroll
+  for (int t = 0; t < 4; ++t)
+#pragma unroll
+    for (int reg = 0; reg < 4; ++reg)
+      if (sees_key<DIAG>(16 * t + 4 * g + reg, rloc, Lk)) mx = fmaxf(mx, st[t][reg]);
+  const float mnew = fmaxf(mrun, row_max4(mx));      // finite: every block walked shows every row its key 0
+  const float alpha = expf(mrun - mnew);             // 0 at the first block (mrun = -inf)
+  float sum = 0.f;
+#pragma unroll
+  for (int t = 0; t < 4; ++t)
+#pragma unroll
+    for (int reg = 0; reg < 4; ++reg) {
+      const float p = sees_key<DIAG>(16 * t + 4 * g + reg, rloc, Lk) ? expf(st[t][reg] - mnew) : 0.f;
+      st[t][reg] = p;
+      sum += p;
+    }
+  lrun = lrun * alpha + row_sum4(sum);
+  mrun = mnew;
+#pragma unroll
+  for (int t = 0; t < 4; ++t) {
+    float m[4] = {1.f, 1.f, 1.f, 1.f};
+    if (rok && walks_tile<DIAG>(t, wave, Lk)) drop_mult4(a, bh, row, 4 * kb + t, g, m);
+#pragma unroll
+    for (int reg = 0; reg < 4; ++reg) st[t][reg] = rok ? st[t][reg] * m[reg] : 0.f;
+  }
+  f32x4 pv[DH / 16];
+  seam_product<DH, DIAG>(Vs, st, wave, Lk, g, j16, pv);
+#pragma unroll
+  for (int u = 0; u < DH / 16; ++u) ot[u] = ot[u] * alpha + pv[u];
+}
+
+template <int DH, bool CAUSAL>
+__global__ __launch_bounds__(256) void attn_tiled_fwd(AttnArgs a) {
+  constexpr int LD = DH + 4;
+  __shared__ float Ks[kMaxL * LD];
+  __shared__ float Vs[kMaxL * LD];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, g = lane >> 4, j16 = lane & 15;
+  const TiledOwner o = tiled_owner<DH>(a);
+  const int L = a.L, E = o.E;
+  const int row = kMaxL * o.blk + 16 * wave + j16;
+  const bool active = kMaxL * o.blk + 16 * wave < L, rok = row < L;
+
+  float qf[DH / 4];
+#pragma unroll
+  for (int k = 0; k < DH / 4; ++k) qf[k] = rok ? a.q[o.base + (int64_t)row * E + 4 * k + g] * a.qscale : 0.f;
+  float mrun = -INFINITY, lrun = 0.f;
+  f32x4 ot[DH / 16];
+#pragma unroll
+  for (int u = 0; u < DH / 16; ++u) ot[u] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  const int last = CAUSAL ? o.blk : o.nB - 1;
+  for (int kb = 0; kb <= last; ++kb) {
+    const int Lk = min(kMaxL, L - kMaxL * kb);
+    __syncthreads();                    // every wave is done with the block before
+    stage_tile<DH>(Ks, a.k + o.base + (int64_t)kMaxL * kb * E, Lk, E);
+    stage_tile<DH>(Vs, a.v + o.base + (int64_t)kMaxL * kb * E, Lk, E);
+    __syncthreads();
+    if (!active) continue;
+    if (CAUSAL && kb == o.blk) tiled_fwd_block<DH, true>(a, Ks, Vs, qf, o.bh, row, rok, kb, Lk, wave, g, j16, mrun, lrun, ot);
+    else tiled_fwd_block<DH, false>(a, Ks, Vs, qf, o.bh, row, rok, kb, Lk, wave, g, j16, mrun, lrun, ot);
+  }
+  if (!rok) return;
+  const float inv = 1.f / lrun;
+#pragma unroll
+  for (int u = 0; u < DH / 16; ++u)
+    *reinterpret_cast<float4*>(a.out + o.base + (int64_t)row * E + 16 * u + 4 * g) =
+        make_float4(ot[u][0] * inv, ot[u][1] * inv, ot[u][2] * inv, ot[u][3] * inv);
+  if (g == 0) a.lse[o.bh * L + row] = mrun + logf(lrun);
+}
+
+// one key block of dQ: the first pass of attn_bwd on the block, with delta handed in
+template <int DH, bool DIAG>
+__device__ __forceinline__ void tiled_bwd_q_block(const AttnArgs& a, const float* Ks, const float* Vs,
+                                                  const float (&qf)[DH / 4], const float (&gof)[DH / 4], const int64_t bh,
+                                                  const int row, const bool rok, const bool lone, const float lse,
+                                                  const float delta, const int kb, const int Lk, const int wave, const int g,
+                                                  const int j16, f32x4 (&gq)[DH / 16]) {
+  const int rloc = 16 * wave + j16;
+  f32x4 st[4], ds[4];
+  scores<DH, DIAG>(Ks, qf, wave, Lk, g, j16, st);
+  scores<DH, DIAG>(Vs, gof, wave, Lk, g, j16, ds);      // dP~ for now
+#pragma unroll
+  for (int t = 0; t < 4; ++t) {
+    float m[4] = {1.f, 1.f, 1.f, 1.f};
+    if (rok && walks_tile<DIAG>(t, wave, Lk)) drop_mult4(a, bh, row, 4 * kb + t, g, m);
+#pragma unroll
+    for (int reg = 0; reg < 4; ++reg) {
+#pragma clang fp contract(off)    // dp is rounded before dp - delta, as in attn_bwd
+      const float p = (rok && sees_key<DIAG>(16 * t + 4 * g + reg, rloc, Lk)) ? expf(st[t][reg] - lse) : 0.f;
+      const float dp = ds[t][reg] * m[reg];
+      ds[t][reg] = lone ? 0.f : p * (dp - delta) * a.qscale;
+    }
+  }
+  f32x4 part[DH / 16];
+  seam_product<DH, DIAG>(Ks, ds, wave, Lk, g, j16, part);
+#pragma unroll
+  for (int u = 0; u < DH / 16; ++u) gq[u] += part[u];
+}
+
+template <int DH, bool CAUSAL>
+__global__ __launch_bounds__(256) void attn_tiled_bwd_q(AttnArgs a) {
+  constexpr int LD = DH + 4;
+  __shared__ float Ks[kMaxL * LD];
+  __shared__ float Vs[kMaxL * LD];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, g = lane >> 4, j16 = lane & 15;
+  const TiledOwner o = tiled_owner<DH>(a);
+  const int L = a.L, E = o.E;
+  const int row = kMaxL * o.blk + 16 * wave + j16;
+  const bool active = kMaxL * o.blk + 16 * wave < L, rok = row < L;
+
+  float qf[DH / 4], gof[DH / 4];
+#pragma unroll
+  for (int k = 0; k < DH / 4; ++k) {
+    qf[k] = rok ? a.q[o.base + (int64_t)row * E + 4 * k + g] * a.qscale : 0.f;
+    gof[k] = rok ? a.go[o.base + (int64_t)row * E + 4 * k + g] : 0.f;
+  }
+  const float lse = rok ? a.lse_in[o.bh * L + row] : 0.f;
+  const float delta =
+      row_sum4(rok ? delta_share<DH>(a.go + o.base + (int64_t)row * E, a.out_in + o.base + (int64_t)row * E, g) : 0.f);
+  f32x4 gq[DH / 16];
+#pragma unroll
+  for (int u = 0; u < DH / 16; ++u) gq[u] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  const int last = CAUSAL ? o.blk : o.nB - 1;
+  for (int kb = 0; kb <= last; ++kb) {
+    const int Lk = min(kMaxL, L - kMaxL * kb);
+    __syncthreads();
+    stage_tile<DH>(Ks, a.k + o.base + (int64_t)kMaxL * kb * E, Lk, E);
+    stage_tile<DH>(Vs, a.v + o.base + (int64_t)kMaxL * kb * E, Lk, E);
+    __syncthreads();
+    if (!active) continue;
+    const bool lone = lone_key<CAUSAL>(row, L);
+    if (CAUSAL && kb == o.blk)
+      tiled_bwd_q_block<DH, true>(a, Ks, Vs, qf, gof, o.bh, row, rok, lone, lse, delta, kb, Lk, wave, g, j16, gq);
+    else
+      tiled_bwd_q_block<DH, false>(a, Ks, Vs, qf, gof, o.bh, row, rok, lone, lse, delta, kb, Lk, wave, g, j16, gq);
+  }
+  if (!rok) return;
+#pragma unroll
+  for (int u = 0; u < DH / 16; ++u)
+    *reinterpret_cast<float4*>(a.gq + o.base + (int64_t)row * E + 16 * u + 4 * g) =
+        make_float4(gq[u][0], gq[u][1], gq[u][2], gq[u][3]);
+}
+
+// dK and dV of one key block.  The roles of scores() and seam_product() are swapped: the lane's register operand is its
+// KEY's row of K (then V), the LDS tile holds the QUERY block's scaled Q (then dO), so st[t][reg] is
+// S[query 16t + 4g + reg][key j16] and the accumulator is again the B operand of the seam, whose sum runs over queries:
+// dV^T += dO^T P~, dK^T += Q^T dS.  No P~ / dS buffer, no barrier between the two products.
+template <int DH, bool CAUSAL>
+__global__ __launch_bounds__(256) void attn_tiled_bwd_kv(AttnArgs a) {
+  constexpr int LD = DH + 4;
+  __shared__ float Qs[kMaxL * LD];      // Q / sqrt(dh) of the query block
+  __shared__ float Gs[kMaxL * LD];      // dO of the query block
+  __shared__ float Ls[kMaxL], Ds[kMaxL];   // its rows' lse and delta
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, g = lane >> 4, j16 = lane & 15;
+  const TiledOwner o = tiled_owner<DH>(a);
+  const int L = a.L, E = o.E;
+  const int kloc = 16 * wave + j16, key = kMaxL * o.blk + kloc;
+  const bool active = kMaxL * o.blk + 16 * wave < L, kok = key < L;
+
+  float kf[DH / 4], vf[DH / 4];
+#pragma unroll
+  for (int k = 0; k < DH / 4; ++k) {
+    kf[k] = kok ? a.k[o.base + (int64_t)key * E + 4 * k + g] : 0.f;
+    vf[k] = kok ? a.v[o.base + (int64_t)key * E + 4 * k + g] : 0.f;
+  }
+  f32x4 gk[DH / 16], gv[DH / 16];
+#pragma unroll
+  for (int u = 0; u < DH / 16; ++u) gk[u] = gv[u] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  for (int qb = CAUSAL ? o.blk : 0; qb < o.nB; ++qb) {
+    const int Lq = min(kMaxL, L - kMaxL * qb);
+    const int64_t qbase = o.base + (int64_t)kMaxL * qb * E;
+    __syncthreads();
+    stage_tile<DH, true>(Qs, a.q + qbase, Lq, E, a.qscale);
+    stage_tile<DH>(Gs, a.go + qbase, Lq, E);
+    {
+      const int r = threadIdx.x >> 2, part = threadIdx.x & 3;      // four neighbouring lanes per query row
+      float d = r < Lq ? delta_share<DH>(a.go + qbase + (int64_t)r * E, a.out_in + qbase + (int64_t)r * E, part) : 0.f;
+      d += __shfl_xor(d, 1);
+      d += __shfl_xor(d, 2);
+      if (part == 0) {
+        Ds[r] = d;
+        Ls[r] = r < Lq ? a.lse_in[o.bh * L + kMaxL * qb + r] : 0.f;
+      }
+    }
+    __syncthreads();
+    if (!active) continue;
+    const bool diag = CAUSAL && qb == o.blk;
+    f32x4 st[4], ds[4];
+    scores<DH, false>(Qs, kf, wave, Lq, g, j16, st);
+    scores<DH, false>(Gs, vf, wave, Lq, g, j16, ds);      // dP~ for now
+#pragma unroll
+    for (int t = 0; t < 4; ++t)
+#pragma unroll
+      for (int reg = 0; reg < 4; ++reg) {
+#pragma clang fp contract(off)
+        const int qloc = 16 * t + 4 * g + reg, qrow = kMaxL * qb + qloc;
+        const bool seen = kok && qloc < Lq && (!diag || kloc <= qloc);
+        const float m = seen ? drop_mult1(a, o.bh, qrow, key) : 0.f;
+        const float p = seen ? expf(st[t][reg] - Ls[qloc]) : 0.f;
+        const float dp = ds[t][reg] * m;
+        st[t][reg] = p * m;                                                      // P~
+        ds[t][reg] = lone_key<CAUSAL>(qrow, L) ? 0.f : p * (dp - Ds[qloc]);     // dS sqrt(dh): Qs carries 1 / sqrt(dh)
+      }
+    f32x4 part[DH / 16];
+    seam_product<DH, false>(Gs, st, wave, Lq, g, j16, part);
+#pragma unroll
+    for (int u = 0; u < DH / 16; ++u) gv[u] += part[u];
+    seam_product<DH, false>(Qs, ds, wave, Lq, g, j16, part);
+#pragma unroll
+    for (int u = 0; u < DH / 16; ++u) gk[u] += part[u];
+  }
+  if (!kok) return;
+#pragma unroll
+  for (int u = 0; u < DH / 16; ++u) {
+    *reinterpret_cast<float4*>(a.gv + o.base + (int64_t)key * E + 16 * u + 4 * g) =
+        make_float4(gv[u][0], gv[u][1], gv[u][2], gv[u][3]);
+    *reinterpret_cast<float4*>(a.gk + o.base + (int64_t)key * E + 16 * u + 4 * g) =
+        make_float4(gk[u][0], gk[u][1], gk[u][2], gk[u][3]);
+  }
+}
+
 srh_status_t attn_check(const char* what, int64_t B, int32_t L, int32_t H, int32_t dh, const uint8_t* d_keep,
-                        float drop_p, AttnArgs& a) {
+                        float drop_p, AttnArgs& a, const int max_l = kMaxL) {
   SRH_REQUIRE(B >= 1 && L >= 1 && H >= 1, "%s: bad shape B=%lld L=%d H=%d", what, (long long)B, L, H);
   SRH_REQUIRE(drop_p >= 0.f && drop_p < 1.f, "%s: drop probability must be in [0, 1)", what);
-  SRH_SUPPORTED(L <= kMaxL, "%s: L=%d -- the kernel holds sequences of up to %d positions", what, L, kMaxL);
+  SRH_SUPPORTED(L <= max_l, "%s: L=%d -- the kernel holds sequences of up to %d positions", what, L, max_l);
   SRH_SUPPORTED(dh == 32 || dh == 64, "%s: head width %d -- the kernel serves 32 and 64", what, dh);
   SRH_SUPPORTED((int64_t)H * dh <= 128, "%s: H dh = %lld -- the kernel serves up to 128", what, (long long)H * dh);
   SRH_SUPPORTED(B * H < (int64_t(1) << 31) && B * L * H * dh < (int64_t(1) << 40), "%s: too many sequences", what);
@@ -597,9 +886,67 @@ srh_status_t attn_bwd_launch(const char* what, const float* d_q, const float* d_
   return SRH_OK;
 }
 
+// the checks and the grid of a tiled call: one workgroup per (sequence, head, 64-row block)
+srh_status_t attn_tiled_check(const char* what, int64_t B, int32_t L, int32_t H, int32_t dh, const uint8_t* d_keep,
+                              uint64_t rng_seed, uint64_t rng_counter, float drop_p, AttnArgs& a, unsigned& grid) {
+  const srh_status_t s = attn_check(what, B, L, H, dh, d_keep, drop_p, a, kTiledMaxL);
+  if (s != SRH_OK) return s;
+  const int64_t blocks = B * H * ((L + kMaxL - 1) / kMaxL);
+  SRH_SUPPORTED(blocks < (int64_t(1) << 31), "%s: too many sequences", what);
+  a.seed_lo = (uint32_t)rng_seed; a.seed_hi = (uint32_t)(rng_seed >> 32); a.ctr = rng_counter;
+  grid = (unsigned)blocks;
+  return SRH_OK;
+}
+
+template <bool CAUSAL>
+void attn_tiled_fwd_launch(const AttnArgs& a, int32_t dh, unsigned grid, hipStream_t st) {
+  if (dh == 64) attn_tiled_fwd<64, CAUSAL><<<grid, 256, 0, st>>>(a);
+  else attn_tiled_fwd<32, CAUSAL><<<grid, 256, 0, st>>>(a);
+}
+
+template <bool CAUSAL>
+srh_status_t attn_tiled_bwd_launch(const AttnArgs& a, int32_t dh, unsigned grid, hipStream_t st) {
+  if (dh == 64) attn_tiled_bwd_q<64, CAUSAL><<<grid, 256, 0, st>>>(a);
+  else attn_tiled_bwd_q<32, CAUSAL><<<grid, 256, 0, st>>>(a);
+  SRH_LAUNCH_CHECK();
+  if (dh == 64) attn_tiled_bwd_kv<64, CAUSAL><<<grid, 256, 0, st>>>(a);
+  else attn_tiled_bwd_kv<32, CAUSAL><<<grid, 256, 0, st>>>(a);
+  SRH_LAUNCH_CHECK();
+  return SRH_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+srh_status_t srh_seq_attn_tiled_fwd_f32(const float* d_q, const float* d_k, const float* d_v, int64_t B, int32_t L,
+                                        int32_t H, int32_t dh, int32_t causal, const uint8_t* d_keep, uint64_t rng_seed,
+                                        uint64_t rng_counter, float drop_p, float* d_out, float* d_lse, void* stream) {
+  SRH_REQUIRE(d_q && d_k && d_v && d_out && d_lse, "seq_attn_tiled_fwd: null argument");
+  AttnArgs a{};
+  unsigned grid = 0;
+  const srh_status_t s = attn_tiled_check("seq_attn_tiled_fwd", B, L, H, dh, d_keep, rng_seed, rng_counter, drop_p, a, grid);
+  if (s != SRH_OK) return s;
+  a.q = d_q; a.k = d_k; a.v = d_v; a.out = d_out; a.lse = d_lse;
+  if (causal) attn_tiled_fwd_launch<true>(a, dh, grid, as_stream(stream));
+  else attn_tiled_fwd_launch<false>(a, dh, grid, as_stream(stream));
+  SRH_LAUNCH_CHECK();
+  return SRH_OK;
+}
+
+srh_status_t srh_seq_attn_tiled_bwd_f32(const float* d_q, const float* d_k, const float* d_v, const float* d_out,
+                                        const float* d_go, const float* d_lse, int64_t B, int32_t L, int32_t H, int32_t dh,
+                                        int32_t causal, const uint8_t* d_keep, uint64_t rng_seed, uint64_t rng_counter,
+                                        float drop_p, float* d_gq, float* d_gk, float* d_gv, void* stream) {
+  SRH_REQUIRE(d_q && d_k && d_v && d_out && d_go && d_lse && d_gq && d_gk && d_gv, "seq_attn_tiled_bwd: null argument");
+  AttnArgs a{};
+  unsigned grid = 0;
+  const srh_status_t s = attn_tiled_check("seq_attn_tiled_bwd", B, L, H, dh, d_keep, rng_seed, rng_counter, drop_p, a, grid);
+  if (s != SRH_OK) return s;
+  a.q = d_q; a.k = d_k; a.v = d_v; a.out_in = d_out; a.go = d_go; a.lse_in = d_lse; a.gq = d_gq; a.gk = d_gk; a.gv = d_gv;
+  return causal ? attn_tiled_bwd_launch<true>(a, dh, grid, as_stream(stream))
+                : attn_tiled_bwd_launch<false>(a, dh, grid, as_stream(stream));
+}
 
 srh_status_t srh_seq_attn_fwd_f32(const float* d_q, const float* d_k, const float* d_v, int64_t B, int32_t L, int32_t H,
                                   int32_t dh, const uint8_t* d_keep, uint64_t rng_seed, uint64_t rng_counter, float drop_p,

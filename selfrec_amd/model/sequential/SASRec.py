@@ -26,8 +26,9 @@ from .encoder import torch_causal_attention  # noqa: F401  (a public name of thi
 
 
 def attention_route(conf=None):
-    """'hip' or 'torch': SRH_SASREC_ATTN, else the conf's engine.attention, else the kernel"""
-    return route('SRH_SASREC_ATTN', 'engine.attention', conf)
+    """'hip', 'torch' or 'tiled': SRH_SASREC_ATTN, else the conf's engine.attention, else the kernel.  'tiled' is 'hip' plus
+    the tiled kernels for 64 < max.len <= 512, which 'hip' leaves to torch's expression"""
+    return route('SRH_SASREC_ATTN', 'engine.attention', conf, ('hip', 'torch', 'tiled'))
 
 
 class StagedBatch(StagedIds):

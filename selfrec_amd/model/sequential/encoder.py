@@ -113,20 +113,38 @@ class SeqEncoder(nn.Module):
         return (self.attention == 'hip' and bool(on_device)
                 and ops.seq_attn_supported(int(L), self.head_num, self.emb_size // self.head_num))
 
+    def attention_kernel(self, L, on_device=True):
+        """which fused kernel the attention core of L positions runs on: 'resident' (one (sequence, head) in LDS, L up to
+        ops.SEQ_ATTN_MAX_LEN; the routes 'hip' and 'tiled'), 'tiled' (64-key blocks, L up to ops.SEQ_ATTN_TILED_MAX_LEN; only
+        under the explicit route 'tiled': measured against torch's expression it is not faster at every length, DESIGN.md
+        4.28), or None for torch's expression (the torch route, a CPU model, a shape outside the route's envelopes)"""
+        if self.attention not in ('hip', 'tiled') or not on_device:
+            return None
+        heads, dh = self.head_num, self.emb_size // self.head_num
+        if ops.seq_attn_supported(int(L), heads, dh):
+            return 'resident'
+        if self.attention == 'tiled' and ops.seq_attn_tiled_supported(int(L), heads, dh):
+            return 'tiled'
+        return None
+
     def _attention(self, mha, query, memory, keep=None):
         """nn.MultiheadAttention(query, memory, memory, attn_mask=causal or None) on (B, L, d) tensors: the packed
-        in-projection and the out-projection are torch's Linear, the core between them the fused kernel or torch's
-        expression"""
+        in-projection and the out-projection are torch's Linear, the core between them a fused kernel (attention_kernel) or
+        torch's expression"""
         E = self.emb_size
         w, b = mha.in_proj_weight, mha.in_proj_bias
         q = F.linear(query, w[:E], b[:E])
         k = F.linear(memory, w[E:2 * E], b[E:2 * E])
         v = F.linear(memory, w[2 * E:], b[2 * E:])
         p = float(mha.dropout) if self.training else 0.0
-        if self.uses_kernel(q.shape[1], q.is_cuda):
+        kernel = self.attention_kernel(q.shape[1], q.is_cuda)     # ('resident' == uses_kernel under the route 'hip')
+        if kernel is not None:
             B, L = int(q.shape[0]), int(q.shape[1])
-            fn = ops.SeqAttnFn if self.causal else ops.SeqAttnFullFn
-            core = fn.apply(q, k, v, self.head_num, keep, p, self.rng_seed, self.rng_counter)
+            if kernel == 'tiled':
+                core = ops.SeqAttnTiledFn.apply(q, k, v, self.head_num, self.causal, keep, p, self.rng_seed, self.rng_counter)
+            else:
+                fn = ops.SeqAttnFn if self.causal else ops.SeqAttnFullFn
+                core = fn.apply(q, k, v, self.head_num, keep, p, self.rng_seed, self.rng_counter)
             if keep is None and p > 0.0:
                 self.rng_counter += B * self.head_num * L
         else:

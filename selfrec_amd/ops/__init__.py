@@ -24,7 +24,8 @@ from .seq import (LIVE_SUM_CHUNK, LIVE_SUM_MAX_PROBLEMS, SEQ_ATTN_HEAD_WIDTHS, S
                   SEQ_EMBED_WIDTHS, GatherRowsFn, SeqAttnFn, SeqAttnFullFn, SeqBceFn, SeqBceLiveFn, SeqEmbedFn, live_plan,
                   live_plan_host, rows_live_sum, rows_segment_sum, scatter_plan, scatter_plan_host, seq_attn_bwd,
                   seq_attn_full_bwd, seq_attn_full_fwd, seq_attn_fwd, seq_attn_supported, seq_bce_fwd_bwd, seq_embed_fwd,
-                  seq_embed_supported)
+                  seq_embed_supported, SEQ_ATTN_TILED_MAX_LEN, SeqAttnTiledFn, seq_attn_tiled_bwd, seq_attn_tiled_fwd,
+                  seq_attn_tiled_supported)
 from .sparse import (ADAM_EPILOGUE, DeviceCSR, adj_sym_normalize, column_class_order, gather_floor_probe, make_epilogue,
                      spmm, spmm3, spmm_any, spmm_gather_bound, spmm_plan_run_tasks, spmm_probe, spmm_set_xcd_shares)
 from .step import (NCE_DEFAULT, NCE_F32_MAX_N, NCE_PRECISIONS, adam_step, axpby, batch_fetch, batch_fetch_args, batch_lists,
@@ -48,5 +49,6 @@ __all__ = """
     rows_l2norm_fwd rows_l2norm_bwd NormPropFn RowsL2NormFn tri_nd_fwd_bwd TriNdFn gate_fwd gate_bwd GateFn
     chan_mix_fwd chan_mix_bwd ChanMixFn mim_fwd_bwd MimFn mixup_supported mixup_fwd mixup_bwd MixupFn au_supported au_fwd_bwd
     AlignUniformFn boot_supported boot_fwd_bwd BootstrapLossFn rows_momentum pair_ce_fwd_bwd PairCeFn SelfPairCeFn
-    triplet_fwd_bwd TripletFn kl_div_fwd_bwd KlDivFn
+    triplet_fwd_bwd TripletFn kl_div_fwd_bwd KlDivFn SEQ_ATTN_TILED_MAX_LEN seq_attn_tiled_supported seq_attn_tiled_fwd
+    seq_attn_tiled_bwd SeqAttnTiledFn
 """.split()

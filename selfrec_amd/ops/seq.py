@@ -143,6 +143,70 @@ class SeqAttnFullFn:
     apply = staticmethod(functools.partial(_SeqAttn.apply, False))
 
 
+SEQ_ATTN_TILED_MAX_LEN = 512                  # srh_seq_attn_tiled_*: L <= 512, the widths of srh_seq_attn_*
+
+
+def seq_attn_tiled_supported(L: int, H: int, dh: int) -> bool:
+    """whether (L, H, dh) is inside the tiled attention kernels' envelope (include/selfrec_hip.h (a-25))"""
+    return 1 <= L <= SEQ_ATTN_TILED_MAX_LEN and dh in SEQ_ATTN_HEAD_WIDTHS and 1 <= H and H * dh <= SEQ_ATTN_MAX_WIDTH
+
+
+def seq_attn_tiled_fwd(q, k, v, n_heads, *, causal=True, keep=None, drop_p=0.0, rng_seed=0, rng_counter=0):
+    """seq_attn_fwd (causal) or seq_attn_full_fwd (causal=False) for up to SEQ_ATTN_TILED_MAX_LEN positions, walked in
+    64-key blocks: (out (B, L, H * dh), lse (B, H, L)), the same dropout contract."""
+    B, L, H, dh, keep = _attn_shape(q, k, v, n_heads, keep)
+    out = torch.empty_like(q)
+    lse = torch.empty((B, H, L), dtype=torch.float32, device=q.device)
+    check(_lib.load().srh_seq_attn_tiled_fwd_f32(_p(q, torch.float32, "q"), _p(k, torch.float32, "k"),
+                                                 _p(v, torch.float32, "v"), B, L, H, dh, int(bool(causal)),
+                                                 _p(keep, torch.uint8, "keep"), u64(rng_seed), u64(rng_counter),
+                                                 float(drop_p), _p(out), _p(lse), _stream()), "srh_seq_attn_tiled_fwd_f32")
+    return out, lse
+
+
+def seq_attn_tiled_bwd(q, k, v, out, lse, go, n_heads, *, causal=True, keep=None, drop_p=0.0, rng_seed=0, rng_counter=0):
+    """(dq, dk, dv) of seq_attn_tiled_fwd for the upstream gradient go, from the forward's out and lse and its dropout
+    arguments."""
+    B, L, H, dh, keep = _attn_shape(q, k, v, n_heads, keep)
+    if out.shape != q.shape:
+        raise SelfrecHipError("seq_attn_tiled_bwd: out must have the shape of q")
+    go = go.to(torch.float32).contiguous()
+    gq, gk, gv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
+    check(_lib.load().srh_seq_attn_tiled_bwd_f32(_p(q, torch.float32, "q"), _p(k, torch.float32, "k"),
+                                                 _p(v, torch.float32, "v"), _p(out, torch.float32, "out"),
+                                                 _p(go, torch.float32, "go"), _p(lse, torch.float32, "lse"), B, L, H, dh,
+                                                 int(bool(causal)), _p(keep, torch.uint8, "keep"), u64(rng_seed),
+                                                 u64(rng_counter), float(drop_p), _p(gq), _p(gk), _p(gv), _stream()),
+          "srh_seq_attn_tiled_bwd_f32")
+    return gq, gk, gv
+
+
+class _SeqAttnTiled(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, q, k, v, n_heads, causal, keep, drop_p, rng_seed, rng_counter):
+        q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
+        ctx.args = dict(causal=causal, keep=keep, drop_p=drop_p, rng_seed=rng_seed, rng_counter=rng_counter)
+        out, lse = seq_attn_tiled_fwd(q, k, v, n_heads, **ctx.args)
+        ctx.save_for_backward(q, k, v, out, lse)
+        ctx.n_heads = n_heads
+        return out
+
+    @staticmethod
+    def backward(ctx, go):
+        q, k, v, out, lse = ctx.saved_tensors
+        gq, gk, gv = seq_attn_tiled_bwd(q, k, v, out, lse, go, ctx.n_heads, **ctx.args)
+        return gq, gk, gv, None, None, None, None, None, None
+
+
+class SeqAttnTiledFn:
+    """seq_attn_tiled_fwd / seq_attn_tiled_bwd as one differentiable op of (q, k, v):
+    apply(q, k, v, n_heads, causal=True, keep=None, drop_p=0.0, rng_seed=0, rng_counter=0)."""
+
+    @staticmethod
+    def apply(q, k, v, n_heads, causal=True, keep=None, drop_p=0.0, rng_seed=0, rng_counter=0):
+        return _SeqAttnTiled.apply(q, k, v, n_heads, causal, keep, drop_p, rng_seed, rng_counter)
+
+
 def seq_bce_fwd_bwd(hidden, table, pos, neg, valid, n_valid=None, ws=None):
     """SASRec.calculate_loss over hidden rows (R x d): (loss2 (2,) float64: the positive and the negative
     BCE-with-logits means over the rows with valid != 0, dL/dhidden (R x d), per-row table gradients (2R x d: rows of

@@ -11,5 +11,5 @@ def route(env, key, conf, choices=('hip', 'torch')):
         value = conf[key]
     value = choices[0] if value is None else str(value).strip().lower()
     if value not in choices:
-        raise ValueError(f"{key} / {env}: {value!r} is neither {choices[0]!r} nor {choices[1]!r}")
+        raise ValueError(f"{key} / {env}: {value!r} is none of {', '.join(repr(c) for c in choices)}")
     return value
