@@ -1299,6 +1299,31 @@ srh_status_t srh_kl_div_fwd_bwd(const float* d_p_logit, const float* d_q_logit, 
                                 float* d_gp, float* d_gq, void* d_ws, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * (a-25) DuoRec's contrastive section -- two info_nce terms (util/loss_torch.py:54-88) that share their anchor rows,
+ * forward and backward in two launches.  DESIGN.md 4.29.
+ *
+ * srh_duo_nce_fwd_bwd: z = [x[idx_a]; x[idx_p]; x[idx_q]] (3B rows of d columns, B >= 1; all three index vectors NULL: z is
+ *   the first 3B rows of x, rows >= 3B), s = inv_temp z z^T.  The u-softmax runs over U = A u P and the s-softmax over
+ *   V = A u Q; a row never sees itself, P rows see no Q key and Q rows no P key; partner_u: a_b <-> p_b, partner_s: a_b <-> q_b.
+ *     lse^t_m = log sum_{j in keys_t(m)} exp(s_mj)
+ *     d_losses[t] = scale_t / 2B * sum_m (lse^t_m - s_{m, partner_t(m)})           (two doubles: u, s)
+ *     d_g (3B x d, rows [ga; gp; gq]) = sum_t scale_t inv_temp / 2B * sum_{j in keys_t(r)}
+ *                                       (exp(s_rj - lse^t_r) + exp(s_rj - lse^t_j) - 2 [j == partner_t(r)]) z_j
+ *   = info_nce(z_a, z_p, 1 / inv_temp, B) * scale_u and info_nce(z_a, z_q, ...) * scale_s with their whole gradients: the
+ *   second exponential is the key side of each loss, taken from the same score by symmetry.  Both WRITTEN.  Every row of
+ *   d_g has one producer and one summation order: no float atomics, the same bits on every call.  Running maxima make any
+ *   finite logits safe.  The caller guarantees 0 <= idx < rows and that the 3B indices are pairwise distinct (a row named
+ *   twice would be its own key).  B == 1: each softmax has one key; both losses and d_g are exact zeros.
+ *   d = 64 or 128, anything else SRH_ERR_UNSUPPORTED; inv_temp not positive and finite, a non-finite scale, one or two
+ *   index vectors: SRH_ERR_INVALID_ARG; all with a message, before any launch.  d_ws >= srh_duo_nce_ws_bytes(B, d) (0 for
+ *   an unsupported shape), any content.
+ * ---------------------------------------------------------------------------------- */
+int64_t srh_duo_nce_ws_bytes(int64_t B, int32_t d);
+srh_status_t srh_duo_nce_fwd_bwd(const float* d_x, int64_t rows, const int32_t* d_idx_a, const int32_t* d_idx_p,
+                                 const int32_t* d_idx_q, int64_t B, int32_t d, float inv_temp, float scale_u, float scale_s,
+                                 double* d_losses, float* d_g, void* d_ws, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * (a-20) MHCN -- the self-gates, the channel attention and the hierarchical mutual-information loss of
  * model/graph/MHCN.py:79-93 and 159-181.  All arithmetic fp32; no float atomics: every reduction over rows runs in fixed
  * chunks whose partials are summed in chunk order, so a call returns the same bits every time.  d = 64 or 128 (zero-pad

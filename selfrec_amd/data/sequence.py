@@ -43,6 +43,16 @@ class Sequence(Data):
                 self.test_set[name][items[0]] = 1
                 self.test_set_item.add(items[0])
 
+    def same_target_index(self):
+        """{last training item id: [indices into original_seq]} in file order (cached): the sequences that share a
+        target, DuoRec's semantic positives.  The target of a sequence is its last item."""
+        if getattr(self, '_same_target', None) is None:
+            index = defaultdict(list)
+            for n, (_, ids) in enumerate(self.original_seq):
+                index[ids[-1]].append(n)
+            self._same_target = dict(index)
+        return self._same_target
+
     def get_item_id(self, i):
         return self.item.get(i)
 

@@ -4,6 +4,7 @@
     python -m selfrec_amd.main SASRec --synthetic beauty-seq
     python -m selfrec_amd.main BERT4Rec --synthetic beauty-seq
     python -m selfrec_amd.main CL4SRec --synthetic beauty-seq
+    python -m selfrec_amd.main DuoRec --synthetic beauty-seq
     python -m selfrec_amd.main SEPT --synthetic douban-book
     python -m selfrec_amd.main MHCN --synthetic douban-book
 
@@ -19,7 +20,7 @@ from . import synth
 from .SELFRec import SELFRec
 from .util.conf import ModelConf
 
-MODELS = ['MF', 'LightGCN', 'XSimGCL', 'SimGCL', 'SGL', 'DirectAU', 'MixGCF', 'BUIR', 'SelfCF', 'NCL', 'UserKNN', 'ItemKNN', 'SSL4Rec', 'SASRec', 'BERT4Rec', 'CL4SRec', 'SEPT', 'MHCN']
+MODELS = ['MF', 'LightGCN', 'XSimGCL', 'SimGCL', 'SGL', 'DirectAU', 'MixGCF', 'BUIR', 'SelfCF', 'NCL', 'UserKNN', 'ItemKNN', 'SSL4Rec', 'SASRec', 'BERT4Rec', 'CL4SRec', 'SEPT', 'MHCN', 'DuoRec']
 
 
 def main(argv=None):

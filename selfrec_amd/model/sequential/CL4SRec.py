@@ -46,9 +46,11 @@ class StagedViews:
     """One training step on the device.  ``views`` = [(seq, pos, last)] * 3: the batch and its two augmented views, ``last``
     the 1-based position of the row InfoNCE reads (None for the batch).  views='one' makes one group of the stacked
     (3B, L) arrays, 'three' one group per view; embed='hip' builds live plans (ops.live_plan_host), 'torch' the scatter
-    plans of ops.GatherRowsFn / ops.SeqBceFn.  Everything travels in one int32 upload."""
+    plans of ops.GatherRowsFn / ops.SeqBceFn.  Everything travels in one int32 upload.  ``anchor_last`` (DuoRec; None changes
+    nothing): the batch's own 1-based last positions -- ``idx`` is then the (3, B) device view [batch; view 1; view 2] of the
+    rows to read and ``idx_host`` its host copy."""
 
-    def __init__(self, views, y, neg, device, route_views='one', route_embed='hip'):
+    def __init__(self, views, y, neg, device, route_views='one', route_embed='hip', anchor_last=None):
         seqs = [np.asarray(v[0]) for v in views]
         poss = [np.asarray(v[1]) for v in views]
         B, L = seqs[0].shape
@@ -73,8 +75,14 @@ class StagedViews:
         yn = np.concatenate([y, neg])
         plans.append(ops.live_plan_host(yn, np.concatenate([valid, valid])) if hip else ops.scatter_plan_host(yn))
         head = [seq_all, pos_all, y, neg, lasts[0], lasts[1]]
+        if anchor_last is not None:
+            # DuoRec: the batch's own last rows (its group's hidden matrix) travel in front of the two views', so the three
+            # index vectors lie side by side on the device
+            self.idx_host = np.stack([np.arange(B) * L + np.asarray(anchor_last, dtype=np.int64) - 1] + lasts)
+            head[4:4] = [self.idx_host[0]]
         cut, dev_plans = upload_with_plans(head, plans, device)
-        self.y, self.neg, self.last = cut[2], cut[3], (cut[4], cut[5])
+        self.y, self.neg, self.last = cut[2], cut[3], (cut[-2], cut[-1])
+        self.idx = cut[4].as_strided((3, B), (B, 1)) if anchor_last is not None else None
         self.groups = [Group(((hi - lo) // L, L), cut[0][lo:hi], cut[1][lo:hi], dev_plans[2 * k:2 * k + 2])
                        for k, (lo, hi) in enumerate(bounds)]
         self.bce_plan = dev_plans[-1]

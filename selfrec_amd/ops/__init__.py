@@ -10,6 +10,7 @@ from .boot import BootstrapLossFn, boot_fwd_bwd, boot_supported, rows_momentum
 from .contrastive import (KMEANS_MAX_POINTS_PER_CENTROID, KMEANS_SPLIT_EPS, BatchSoftmaxFn, InfoNceFn, TableCeFn,
                           batch_softmax_fwd_bwd, kmeans, kmeans_assign, kmeans_split, kmeans_update, table_ce_fwd_bwd,
                           table_nce_fwd_bwd, table_nce_ws)
+from .duo import DUO_WIDTHS, DuoNceFn, duo_nce_fwd_bwd, duo_supported
 from .host import Sampler, find_k_largest_host, find_k_largest_host_f64, unique_first
 from .knn import KNN_MAX_K, knn_neighbours, knn_score_topk, knn_score_ws
 from .losses import (TRIPLET_MARGIN, KlDivFn, PairCeFn, SelfPairCeFn, TripletFn, kl_div_fwd_bwd, pair_ce_fwd_bwd,
@@ -50,5 +51,5 @@ __all__ = """
     chan_mix_fwd chan_mix_bwd ChanMixFn mim_fwd_bwd MimFn mixup_supported mixup_fwd mixup_bwd MixupFn au_supported au_fwd_bwd
     AlignUniformFn boot_supported boot_fwd_bwd BootstrapLossFn rows_momentum pair_ce_fwd_bwd PairCeFn SelfPairCeFn
     triplet_fwd_bwd TripletFn kl_div_fwd_bwd KlDivFn SEQ_ATTN_TILED_MAX_LEN seq_attn_tiled_supported seq_attn_tiled_fwd
-    seq_attn_tiled_bwd SeqAttnTiledFn
+    seq_attn_tiled_bwd SeqAttnTiledFn duo_supported duo_nce_fwd_bwd DuoNceFn
 """.split()

@@ -141,6 +141,54 @@ def next_batch_sequence(data, batch_size, n_negs=1, max_len=50):
         yield seq, pos, y, neg, np.array(seq_len, int)
 
 
+def next_batch_sequence_indexed(data, batch_size, n_negs=1, max_len=50):
+    """next_batch_sequence's batches with a sixth array ``rows``: the index into data.original_seq of every batch row.
+    It shuffles the index list instead of the id lists -- a list of the same length, so the same permutation -- and draws
+    the same samples: every batch and the state of ``random`` after an epoch equal next_batch_sequence's."""
+    order = list(range(len(data.original_seq)))
+    _pyrandom.shuffle(order)
+    item_list = list(range(1, data.item_num + 1))
+    for lo in range(0, len(order), batch_size):
+        chunk = order[lo:lo + batch_size]
+        seq, pos, y, neg = (np.zeros((len(chunk), max_len), dtype=int) for _ in range(4))
+        seq_len = []
+        for n, row in enumerate(chunk):
+            ids = data.original_seq[row][1]
+            start, end = _window(len(ids), max_len, True)
+            inputs = ids[start:-1]
+            seq[n, :end] = inputs
+            pos[n, :end] = np.arange(1, end + 1)
+            y[n, :end] = ids[start + 1:]
+            seen = set(inputs)
+            negatives = _pyrandom.sample(item_list, end)
+            while not seen.isdisjoint(negatives):
+                negatives = _pyrandom.sample(item_list, end)
+            neg[n, :end] = negatives
+            seq_len.append(end)
+        yield seq, pos, y, neg, np.array(seq_len, int), np.array(chunk, int)
+
+
+def same_target_positives(data, rows, max_len=50):
+    """DuoRec's semantic positives of the batch rows ``rows`` (indices into data.original_seq): for each row in order, one
+    ``random.choice`` among the other sequences with its target (data.same_target_index()); a target no other sequence
+    shares gives the row's own sequence and consumes no draw.  Returns (seq, pos, seq_len, chosen): the positives' windowed
+    inputs ids[start:-1] padded on the right (the rule of next_batch_sequence), and the chosen indices."""
+    index = data.same_target_index()
+    seq, pos = (np.zeros((len(rows), max_len), dtype=int) for _ in range(2))
+    seq_len, chosen = [], []
+    for n, row in enumerate(rows):
+        row = int(row)
+        cands = [j for j in index[data.original_seq[row][1][-1]] if j != row]
+        pick = _pyrandom.choice(cands) if cands else row
+        ids = data.original_seq[pick][1]
+        start, end = _window(len(ids), max_len, True)
+        seq[n, :end] = ids[start:-1]
+        pos[n, :end] = np.arange(1, end + 1)
+        seq_len.append(end)
+        chosen.append(pick)
+    return seq, pos, np.array(seq_len, int), np.array(chosen, int)
+
+
 def next_batch_sequence_for_test(data, batch_size, max_len=50):
     """Batches (seq, pos, seq_len) over data.original_seq in its order: every sequence's last max_len items."""
     rows = [ids for _, ids in data.original_seq]
