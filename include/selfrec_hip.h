@@ -1324,6 +1324,39 @@ srh_status_t srh_duo_nce_fwd_bwd(const float* d_x, int64_t rows, const int32_t* 
                                  double* d_losses, float* d_g, void* d_ws, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * (a-26) GRU4Rec's recurrence -- the hidden-side half of one torch.nn.GRU layer (gate order r, z, n; both biases) over
+ * right-padded sequences, forward and backward in one launch each.  DESIGN.md 4.30.  The input-side product
+ * gi = X W_ih^T + b_ih and the weight-gradient products are the caller's GEMMs.
+ *
+ * srh_gru_fwd_f32: d_gi (B x L x 3H), d_w_hh (3H x H), d_b_hh (3H), d_len (B, int32, 0 <= len_b <= L).  Per sequence b,
+ *   t < len_b, h_{-1} = 0:
+ *     gh = W_hh h_{t-1} + b_hh;  r = sigmoid(gi_r + gh_r);  z = sigmoid(gi_z + gh_z);  n = tanh(gi_n + r (.) gh_n)
+ *     h_t = (1 - z) (.) n + z (.) h_{t-1};   d_out[b,t] = h_t;   d_gates[b,t] = [r, z, n, gh_n]
+ *   d_out (B x L x H) and d_gates (B x L x 4H) are WRITTEN whole: their rows at t >= len_b are exact zeros; gi there is
+ *   never read.  d_gates == NULL (evaluation): nothing is saved, d_out holds the same bits.
+ * srh_gru_bwd_f32: from the upstream gradient d_go (B x L x H) and the forward's d_out and d_gates.  Per sequence b,
+ *   carry = 0, t = len_b - 1 .. 0, hp = out[b,t-1] (0 at t = 0):
+ *     dh = carry + go[b,t];  dn = dh (1 - z)(1 - n^2);  dz = dh (hp - n) z (1 - z);  dr = dn gh_n r (1 - r)
+ *     d_dgi[b,t] = [dr, dz, dn];   d_dghn[b,t] = dn r;   carry = dh z + [dr, dz, dn r] W_hh
+ *   d_dgi (B x L x 3H) and d_dghn (B x L x H) are WRITTEN whole, exact zeros at t >= len_b; d_go there is never read (it
+ *   may hold anything, NaN included).  The caller finishes with GEMMs on the zero-padded outputs: dX = dgi W_ih,
+ *   dW_ih = dgi^T X, db_ih = sum dgi, and with dGH = [dgi_r, dgi_z, dghn]: dW_hh = dGH^T H_prev, db_hh = sum dGH.
+ *   One workgroup owns 16 sequences for all their steps; both products run on v_mfma_f32_16x16x4_f32 with W_hh resident
+ *   in registers.  One summation order, no float atomics: the same bits on every call.
+ *   H == 64 (a narrower layer is zero-padded by the caller: a padded unit stays an exact 0) and 1 <= L <= 512, anything
+ *   else SRH_ERR_UNSUPPORTED; B < 1 or a null required pointer SRH_ERR_INVALID_ARG; all with a message, before any launch.
+ *   d_gi, d_w_hh and every output must be 16-byte aligned (the kernels read W_hh and write the dead rows as 16-byte
+ *   vectors); a misaligned one is SRH_ERR_INVALID_ARG.
+ *   The lengths stay on the device, so 0 <= len_b <= L is the caller's contract; the kernels clamp a length into that
+ *   range before they use it, so a bad one reads and writes nothing outside the tensors.
+ * ---------------------------------------------------------------------------------- */
+srh_status_t srh_gru_fwd_f32(const float* d_gi, const float* d_w_hh, const float* d_b_hh, const int32_t* d_len, int64_t B,
+                             int32_t L, int32_t H, float* d_out, float* d_gates, void* stream);
+srh_status_t srh_gru_bwd_f32(const float* d_go, const float* d_out, const float* d_gates, const float* d_w_hh,
+                             const int32_t* d_len, int64_t B, int32_t L, int32_t H, float* d_dgi, float* d_dghn,
+                             void* stream);
+
+/* ------------------------------------------------------------------------------------
  * (a-20) MHCN -- the self-gates, the channel attention and the hierarchical mutual-information loss of
  * model/graph/MHCN.py:79-93 and 159-181.  All arithmetic fp32; no float atomics: every reduction over rows runs in fixed
  * chunks whose partials are summed in chunk order, so a call returns the same bits every time.  d = 64 or 128 (zero-pad

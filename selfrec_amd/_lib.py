@@ -239,6 +239,8 @@ SIGNATURES = {
     "srh_pair_ce_fwd_bwd": (_i32, [_vp, _i64, _vp, _i64, _i32, _vp, _f32, _f32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
     "srh_duo_nce_ws_bytes": (_i64, [_i64, _i32]),
     "srh_duo_nce_fwd_bwd": (_i32, [_vp, _i64, _vp, _vp, _vp, _i64, _i32, _f32, _f32, _f32, _vp, _vp, _vp, _vp]),
+    "srh_gru_fwd_f32": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp]),
+    "srh_gru_bwd_f32": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp]),
     "srh_triplet_ws_bytes": (_i64, [_i64]),
     "srh_triplet_fwd_bwd": (_i32, [_vp, _vp, _vp, _i64, _i32, _f32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "srh_kl_div_ws_bytes": (_i64, [_i64]),

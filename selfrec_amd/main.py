@@ -20,7 +20,7 @@ from . import synth
 from .SELFRec import SELFRec
 from .util.conf import ModelConf
 
-MODELS = ['MF', 'LightGCN', 'XSimGCL', 'SimGCL', 'SGL', 'DirectAU', 'MixGCF', 'BUIR', 'SelfCF', 'NCL', 'UserKNN', 'ItemKNN', 'SSL4Rec', 'SASRec', 'BERT4Rec', 'CL4SRec', 'SEPT', 'MHCN', 'DuoRec']
+MODELS = ['MF', 'LightGCN', 'XSimGCL', 'SimGCL', 'SGL', 'DirectAU', 'MixGCF', 'BUIR', 'SelfCF', 'NCL', 'UserKNN', 'ItemKNN', 'SSL4Rec', 'SASRec', 'BERT4Rec', 'CL4SRec', 'SEPT', 'MHCN', 'DuoRec', 'GRU4Rec']
 
 
 def main(argv=None):

@@ -19,6 +19,8 @@ from .mhcn import GATE_MAX, ChanMixFn, GateFn, MimFn, chan_mix_bwd, chan_mix_fwd
 from .mixgcf import MIXUP_MAX_HOPS, MixupFn, mixup_bwd, mixup_fwd, mixup_supported
 from .ranking import (gemm_nt, metric_rows, score_mask_topk, score_mask_topk_filtered, topk_hit_flags, topk_rows,
                       topk_trim_mark_ties)
+from .rnn import (GRU_MAX_LEN, GRU_WIDTH, GatherLiveRowsFn, GruFn, gru_bwd, gru_fwd, gru_lengths, gru_pad_params,
+                  gru_supported)
 from .sept import (L2NORM_MAX_WIDTH, TRI_ND_MAX_K, NormPropFn, RowsL2NormFn, TriNdFn, rows_l2norm_bwd, rows_l2norm_fwd,
                    tri_nd_fwd_bwd)
 from .seq import (LIVE_SUM_CHUNK, LIVE_SUM_MAX_PROBLEMS, SEQ_ATTN_HEAD_WIDTHS, SEQ_ATTN_MAX_LEN, SEQ_ATTN_MAX_WIDTH,
@@ -51,5 +53,6 @@ __all__ = """
     chan_mix_fwd chan_mix_bwd ChanMixFn mim_fwd_bwd MimFn mixup_supported mixup_fwd mixup_bwd MixupFn au_supported au_fwd_bwd
     AlignUniformFn boot_supported boot_fwd_bwd BootstrapLossFn rows_momentum pair_ce_fwd_bwd PairCeFn SelfPairCeFn
     triplet_fwd_bwd TripletFn kl_div_fwd_bwd KlDivFn SEQ_ATTN_TILED_MAX_LEN seq_attn_tiled_supported seq_attn_tiled_fwd
-    seq_attn_tiled_bwd SeqAttnTiledFn duo_supported duo_nce_fwd_bwd DuoNceFn
+    seq_attn_tiled_bwd SeqAttnTiledFn duo_supported duo_nce_fwd_bwd DuoNceFn GRU_WIDTH GRU_MAX_LEN gru_supported
+    gru_lengths gru_fwd gru_bwd gru_pad_params GruFn GatherLiveRowsFn
 """.split()
